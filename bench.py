@@ -1,6 +1,6 @@
 """bench.py — sketches/sec end-to-end (GroundingDINO Swin-T + SAM ViT-H) at 1024x1024 on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N)
     or directly - bench.py then starts its N ranks itself (fresh child processes, before anything touches the GPU).
 
@@ -14,7 +14,8 @@ format; 134 MB per step), boxes/scores on the host.  Uploads and downloads ride 
 neighbouring step's compute (two slots); every one of the K timed steps is complete - masks in host memory - when the
 clock stops.  `device_resident` repeats the measurement without the PCIe legs (round 1's number).
 Image-parallel over ranks (weak scaling), one RCCL weight broadcast at start-up, no per-batch collectives.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; its `ms_per_step` is the wall time of one of the K timed steps.  --dump-outputs DIR
+also writes what the last timed step returned as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -183,6 +184,36 @@ def runner_leg(pipe, batch, n_boxes):
                     "(PNG encoding on 8 host threads); one GPU, not the metric"}
 
 
+DUMP_MASKS = 8                    # whole masks kept by --dump-outputs: 8 x 1024^2 float32 = 32 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: what a caller of the timed path received from its last step (collect_host: per sketch boxes,
+    scores, pixel boxes, uint8 0/1 masks), as float32 / float64 .npy files, so that two builds run with the same
+    arguments (hence the same seeded sketches and weights) can be compared file by file.  Boxes, scores and the
+    pixel count of every mask are complete; of the masks themselves (134 MB at batch 8) a fixed, seeded sample of
+    DUMP_MASKS whole masks is kept, `masks_sample_index` giving their positions in the sketch-major list of masks."""
+    masks = [(i, k) for i, r in enumerate(res) for k in range(r[3].shape[0])]
+    pick = np.sort(np.random.default_rng(0).choice(len(masks), min(DUMP_MASKS, len(masks)), replace=False))
+    arrays = {
+        "boxes_per_sketch": np.array([len(r[1]) for r in res], np.float64),
+        "boxes_xyxy_norm": np.concatenate([np.asarray(r[0], np.float64).reshape(-1, 4) for r in res]),
+        "scores": np.concatenate([np.asarray(r[1], np.float64).reshape(-1) for r in res]),
+        "boxes_pixel": np.concatenate([np.asarray(r[2], np.float32).reshape(-1, 4) for r in res]),
+        "mask_pixel_counts": np.array([r[3][k].sum(dtype=np.int64) for r in res for k in range(r[3].shape[0])],
+                                      np.float64),
+        "masks_sample_index": pick.astype(np.float64),
+        "masks_sample": np.stack([res[masks[j][0]][3][masks[j][1]] for j in pick]).astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
 ATTN_ALGO_BYTES = lambda rows, width: 4.0 * rows * width * 2      # read q, k, v + write o once, f16 (SURVEY §8d)
 PEAK_HBM_TBS = 8.0
 
@@ -222,7 +253,11 @@ def main():
     ap.add_argument("--boxes", type=int, default=16, help="boxes per sketch (top-n by score)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-runner", action="store_true", help="skip the secondary whole-runner (config 5) measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's sketches) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from inklayer_amd import dist as idist
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -268,6 +303,8 @@ def main():
     dt = time.perf_counter() - t0
     dt = idist.max_over_ranks(dt, dev)
     assert len(res) == B and res[0][3].shape == (args.boxes, 1024, 1024) and res[0][3].dtype == np.uint8
+    if args.dump_outputs and rank == 0:      # before the check step below reuses the pinned host buffers
+        dump_outputs(res, args.dump_outputs)
     # the LAST timed step (submitted with its predecessor still in flight) against one synchronous step: same bytes?
     # (round 3: kernels co-resident with the window-attention kernel returned wrong results in a third of in-flight steps
     # until that kernel claimed its SIMDs' register file - DESIGN.md section 7; the bench now says so if it ever recurs)

@@ -142,6 +142,8 @@ def test_run_dir_launcher_two_ranks(tmp_path):
     child = tmp_path / "child.py"
     child.write_text(f"import sys\nsys.path.insert(0, {str(ROOT)!r})\n" + FAKES + textwrap.dedent(f'''
         install()
+        # the ranks run the plumbing on the CPU even where a GPU is visible (rank 1 would ask for a second card)
+        torch.cuda.is_available = lambda: False
         sys.path.insert(0, {str(ROOT / "tools")!r})
         import run_dir
         sys.argv = ["run_dir.py", "--dir", {str(tmp_path / "in")!r}, "--out_dir", {str(tmp_path / "out")!r}, "--batch", "2"]

@@ -1,5 +1,5 @@
 """Pins oracle/refine_ref.py (mask cleanup + sketch NMS) to the reference's OWN committed outputs:
-the 7 sets masks/ -> masks_cleaned/ -> bboxes_final.json that /root/reference holds (tests/golden/refine_*.npz,
+the 7 sets masks/ -> masks_cleaned/ -> bboxes_final.json that the reference holds (tests/golden/refine_*.npz,
 copied as data by tests/golden/make_refine_golden.py).  Bit-exact: every cleaned mask, every kept index."""
 import glob
 from pathlib import Path

@@ -5,8 +5,6 @@ layers, 32 ViT-H blocks) with seeded random weights (INKLAYER_RANDOM_WEIGHTS=1: 
 checked against the CPU oracle run on the same weights: output tree, bboxes.json, masks.  GPU box only."""
 import json
 import os
-import runpy
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -73,13 +71,8 @@ def test_runner_plugins_full_depth_against_oracle(dev, tmp_path, monkeypatch):
     # ---- the product path, through the plugin surfaces
     eng.cfg.box_threshold = thr
     try:
-        monkeypatch.setattr(sys, "argv", ["main.py", "--img", str(png), "--out_dir", str(tmp_path / "out")])
-        ref_main = Path("/root/reference/main.py")
-        if ref_main.exists():                    # build container only: the reference's own main.py, unchanged
-            runpy.run_path(str(ref_main), run_name="__main__")
-            out_dir = tmp_path / "out" / "generated"
-        else:                                    # GPU box: the call main.py makes (main.py:24)
-            out_dir = Path(R.run_inklayer_pipeline(str(png), str(tmp_path / "out")))
+        # the call the reference's main.py makes for `--img png --out_dir out` (main.py:24)
+        out_dir = Path(R.run_inklayer_pipeline(str(png), str(tmp_path / "out"), no_intermediate=False, inpaint=False))
         dino_out = DET.run_ft_dino_on_sketch(str(png))
     finally:
         eng.cfg.box_threshold = gcfg.box_threshold

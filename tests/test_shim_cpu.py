@@ -1,9 +1,7 @@
 """Host-side logic of the drop-in `InkLayer` package (no GPU): box glue numerics, runner output tree,
-and — in the build container only — the reference's own main.py running unchanged on top of it."""
+and the call the reference's main.py makes into it."""
 import json
 import os
-import runpy
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -89,8 +87,12 @@ def _fake_plugins(monkeypatch):
     import InkLayer.refinement.refiner as RF
     from inklayer_amd import refine_stage
     from oracle import refine4_ref
-    monkeypatch.setattr(RF, "get_depth_map_device", lambda path, sketch_rgb=None: torch.from_numpy(
-        np.tile(np.linspace(0, 3, Image.open(path).size[0], dtype=np.float32), (Image.open(path).size[1], 1))))
+    def fake_depth(path, sketch_rgb=None):
+        # like the real one, use the handed-over sketch: input.png may still be being written on the I/O threads
+        W, H = Image.open(path).size if sketch_rgb is None else sketch_rgb.shape[1::-1]
+        return torch.from_numpy(np.tile(np.linspace(0, 3, W, dtype=np.float32), (H, 1)))
+
+    monkeypatch.setattr(RF, "get_depth_map_device", fake_depth)
     monkeypatch.setattr(RF, "_stack_on_gpu", lambda masks, shape: torch.from_numpy(
         np.stack([(np.asarray(m) > 0) for m in masks]).astype(np.uint8)) if len(masks) else torch.zeros((0,) + tuple(shape), dtype=torch.uint8))
 
@@ -144,15 +146,18 @@ def test_runner_output_tree_and_wipe(tmp_path, monkeypatch):
         R.run_inpaint_single_layer({}, ".", ".")
 
 
-@pytest.mark.skipif(not Path("/root/reference/main.py").exists(), reason="reference only exists in the build container")
-def test_reference_main_py_runs_unchanged_on_the_shim(tmp_path, monkeypatch):
-    """BASELINE config 1 (plumbing): the reference's main.py, executed as-is, drives this package."""
+def test_main_py_call_runs_on_the_shim(tmp_path, monkeypatch):
+    """BASELINE config 1 (plumbing): the call the reference's main.py makes for `--img X --out_dir Y` (main.py:24,
+    run_inklayer_pipeline with its no_intermediate / inpaint keywords) drives this package, on the reference's own
+    data/bunny_cook_sketch.png (750x750 RGBA, opaque), rebuilt from the pixels stored in tests/golden."""
+    import InkLayer.runner as R
     _fake_plugins(monkeypatch)
-    monkeypatch.syspath_prepend(str(ROOT))
+    rgb = np.load(GOLD / "refine_bunny_cook_sketch.npz")["input"]
+    src = tmp_path / "bunny_cook_sketch.png"
+    Image.fromarray(np.dstack([rgb, np.full(rgb.shape[:2], 255, np.uint8)]), "RGBA").save(src)
     out = tmp_path / "o"
-    monkeypatch.setattr(sys, "argv", ["main.py", "--img", "/root/reference/data/bunny_cook_sketch.png",
-                                      "--out_dir", str(out)])
-    runpy.run_path("/root/reference/main.py", run_name="__main__")
+    out_dir = R.run_inklayer_pipeline(str(src), str(out), no_intermediate=False, inpaint=False)
+    assert Path(out_dir) == out / "bunny_cook_sketch"
     _check_tree(out / "bunny_cook_sketch", 750, 750)
 
 
