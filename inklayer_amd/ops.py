@@ -426,12 +426,14 @@ def im2col3x3(x: torch.Tensor, B: int, H: int, W: int, out: Optional[torch.Tenso
 
 
 def sam_pe_encode(coords01: torch.Tensor, gauss: torch.Tensor,
-                  add: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[sin, cos](2*pi*((2c-1) @ G)) (+ add[n % n_add]) -> f32 [N, 2F]."""
     assert coords01.dtype == F32 and coords01.is_contiguous() and coords01.shape[-1] == 2
     assert gauss.dtype == F32 and gauss.is_contiguous() and gauss.shape[0] == 2
     N, Fd = coords01.numel() // 2, gauss.shape[1]
-    out = torch.empty((N, 2 * Fd), device=coords01.device, dtype=F32)
+    if out is None:
+        out = torch.empty((N, 2 * Fd), device=coords01.device, dtype=F32)
+    assert out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (N, 2 * Fd)
     n_add = 0
     if add is not None:
         assert add.dtype == F32 and add.is_contiguous() and add.shape[-1] == 2 * Fd
@@ -513,10 +515,13 @@ def swin_patchify(image_u8: torch.Tensor, mean: Sequence[float], std: Sequence[f
     return out
 
 
-def layernorm_merge4(x: torch.Tensor, gamma, beta, eps: float, gather4: torch.Tensor) -> torch.Tensor:
+def layernorm_merge4(x: torch.Tensor, gamma, beta, eps: float, gather4: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     assert x.dtype == F32 and x.stride(1) == 1 and gather4.dtype == torch.int32 and gather4.is_contiguous()
     rows, Cn = gather4.shape[0], x.shape[1]
-    out = torch.empty((rows, 4 * Cn), device=x.device, dtype=F16)
+    if out is None:
+        out = torch.empty((rows, 4 * Cn), device=x.device, dtype=F16)
+    assert out.dtype == F16 and out.is_contiguous() and tuple(out.shape) == (rows, 4 * Cn)
     check(_lib.lib().ink_layernorm_merge4(x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), eps,
                                           gather4.data_ptr(), rows, Cn, out.data_ptr(), _stream()),
           "ink_layernorm_merge4")
@@ -536,10 +541,15 @@ def groupnorm_nhwc(x: torch.Tensor, B: int, T: int, G: int, gamma, beta, eps: fl
 
 
 def gather_rows(x: torch.Tensor, idx: torch.Tensor, B: int, rows_per_batch: int, *, x_batch_rows: int,
-                idx_batch_stride: int, out_dtype=F16) -> torch.Tensor:
+                idx_batch_stride: int, out_dtype=F16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b*rows_per_batch + r] = x[b*x_batch_rows + idx[b*idx_batch_stride + r]] (-1 -> zero row); `out` (f16 or
+    f32, contiguous) overrides out_dtype."""
     assert x.dtype == F32 and x.stride(1) == 1 and idx.dtype == torch.int32 and idx.is_cuda
     Cn = x.shape[1]
-    out = torch.empty((B * rows_per_batch, Cn), device=x.device, dtype=out_dtype)
+    if out is None:
+        out = torch.empty((B * rows_per_batch, Cn), device=x.device, dtype=out_dtype)
+    out_dtype = out.dtype
+    assert out_dtype in (F16, F32) and out.is_contiguous() and tuple(out.shape) == (B * rows_per_batch, Cn)
     oh = out.data_ptr() if out_dtype == F16 else None
     of = out.data_ptr() if out_dtype == F32 else None
     check(_lib.lib().ink_gather_rows(x.data_ptr(), x.stride(0), x_batch_rows, idx.data_ptr(), idx_batch_stride,
@@ -747,19 +757,24 @@ def topk_rowmax(logits: torch.Tensor, K: int, want_values: bool = False):
     return (idx, val) if want_values else idx
 
 
-def sine_embed4(ref: torch.Tensor, dim_t: torch.Tensor) -> torch.Tensor:
+def sine_embed4(ref: torch.Tensor, dim_t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     assert ref.dtype == F32 and ref.is_contiguous() and ref.shape[-1] == 4 and dim_t.numel() == 128
     N = ref.numel() // 4
-    out = torch.empty((N, 512), device=ref.device, dtype=F16)
+    if out is None:
+        out = torch.empty((N, 512), device=ref.device, dtype=F16)
+    assert out.dtype == F16 and out.is_contiguous() and tuple(out.shape) == (N, 512)
     check(_lib.lib().ink_sine_embed4(ref.data_ptr(), dim_t.data_ptr(), N, out.data_ptr(), _stream()),
           "ink_sine_embed4")
     return out
 
 
-def box_refine(delta: torch.Tensor, ref: torch.Tensor, ref_is_logit: bool = False) -> torch.Tensor:
+def box_refine(delta: torch.Tensor, ref: torch.Tensor, ref_is_logit: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     assert delta.dtype == F32 and delta.stride(1) == 1 and ref.dtype == F32 and ref.is_contiguous()
     N = ref.numel() // 4
-    out = torch.empty_like(ref)
+    if out is None:
+        out = torch.empty_like(ref)
+    assert out.dtype == F32 and out.is_contiguous() and out.shape == ref.shape
     check(_lib.lib().ink_box_refine(delta.data_ptr(), delta.stride(0), ref.data_ptr(), N, int(ref_is_logit),
                                     out.data_ptr(), _stream()), "ink_box_refine")
     return out
