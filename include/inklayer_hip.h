@@ -3,7 +3,7 @@
  *
  * Drop-in boundary for the InkLayer detector→segmentor hot path.  The
  * reference (ooowedyn/InkLayer) is Python on torch.nn modules plus ONE native
- * op (groundingdino._C.ms_deform_attn_forward).  Every entry point below
+ * extension (groundingdino._C: ms_deform_attn_forward / _backward).  Every entry point below
  * replaces one reference call site (cited as file:line under
  * /root/reference; GD/ = InkLayer/third_party/GroundingDINO/groundingdino/,
  * SA/ = InkLayer/third_party/segment-anything/segment_anything/).
@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define INK_ABI_VERSION 4
+#define INK_ABI_VERSION 5
 int ink_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -251,6 +251,35 @@ int ink_ms_deform_attn_forward(const float* value, const int64_t* spatial_shapes
                                const float* attn_weight, int32_t B, int32_t S, int32_t M, int32_t C,
                                int32_t Q, int32_t L, int32_t P, int32_t im2col_step, float* out,
                                void* stream);
+
+/* ABI 5: the whole of groundingdino._C (vision.cpp:54-55) with the reference's DEVICE tables.
+ * spatial_shapes int64 [L,2] (h,w) and level_start_index int64 [L] are device pointers, read by the
+ * kernels (no host synchronisation); dtype selects the element type of every float buffer: 0 = f32,
+ * 1 = f64 (anything else returns 1).  Any C >= 1 and L >= 1.  Shapes and layouts as above:
+ * value [B,S,M,C], sampling_loc [B,Q,M,L,P,2] (x,y), attn_weight [B,Q,M,L,P], out / grad_output
+ * [B,Q,M*C].  im2col_step is only validated (B % min(B, step) == 0).  Semantics of
+ * oracle/gdino_ref.py:msda_core: h_im = y*H - 0.5, w_im = x*W - 0.5, a sample outside (-1,H) x (-1,W)
+ * and a corner outside the map contribute 0.  The tables cannot be checked on the host: a level whose
+ * rows would leave [0, S) (h or w <= 0, start < 0, start + h*w > S) contributes 0 and gets zero
+ * gradients, so an inconsistent table gives wrong numbers but never an out-of-bounds access.
+ * At f32 with C == 32 the forward gives the same bits as ink_ms_deform_attn_forward.
+ *
+ * The backward writes all three gradients completely (grad_value [B,S,M,C], grad_sampling_loc
+ * [B,Q,M,L,P,2], grad_attn_weight [B,Q,M,L,P]); it zeroes grad_value on `stream` itself, so the
+ * caller may pass uninitialised memory.  grad_value is accumulated with float atomics: its last bits
+ * depend on arrival order and are NOT reproducible run to run (nor are the reference's); the other
+ * two gradients are plain stores and are. */
+int ink_ms_deform_attn_forward_dev(const void* value, const int64_t* spatial_shapes,
+                                   const int64_t* level_start_index, const void* sampling_loc,
+                                   const void* attn_weight, int32_t dtype, int32_t B, int32_t S, int32_t M,
+                                   int32_t C, int32_t Q, int32_t L, int32_t P, int32_t im2col_step,
+                                   void* out, void* stream);
+int ink_ms_deform_attn_backward_dev(const void* value, const int64_t* spatial_shapes,
+                                    const int64_t* level_start_index, const void* sampling_loc,
+                                    const void* attn_weight, const void* grad_output, int32_t dtype,
+                                    int32_t B, int32_t S, int32_t M, int32_t C, int32_t Q, int32_t L,
+                                    int32_t P, int32_t im2col_step, void* grad_value,
+                                    void* grad_sampling_loc, void* grad_attn_weight, void* stream);
 
 /* Pipeline form of the same op (MultiScaleDeformableAttention.forward, ms_deform_attn.py:282-352,
  * minus the three Linear layers): value f16 [B,S,8,32]; proj f32 [B*Q, ldp] with columns

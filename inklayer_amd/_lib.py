@@ -67,6 +67,11 @@ SIGNATURES = {
                             c_void_p, c_void_p, c_void_p],
     "ink_ms_deform_attn_forward": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), c_void_p, c_void_p, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_ms_deform_attn_forward_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_ms_deform_attn_backward_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p],
     "ink_msda_fused": [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_i64, c_i64, C.POINTER(c_int), c_int,
                        c_int, c_int, c_void_p, c_void_p],
     "ink_swin_patchify": [c_void_p, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p, c_void_p],

@@ -471,23 +471,133 @@ def sam_postprocess(low: torch.Tensor, L: int, input_hw: Tuple[int, int], orig_h
 # ---------------------------------------------------------------------------------------------
 # GroundingDINO-side ops
 # ---------------------------------------------------------------------------------------------
+_MSDA_DTYPE = {F32: 0, torch.float64: 1}
+
+
+def _msda_check(value: torch.Tensor, spatial_shapes, level_start_index, sampling_loc: torch.Tensor,
+                attn_weight: torch.Tensor, im2col_step: int, *grads: torch.Tensor):
+    """The reference's checks (ms_deform_attn_cuda.cu:32-53), raised before anything is launched: float tensors of
+    one dtype (f32 / f64), contiguous, on the GPU; int64 shape tables; B % min(B, im2col_step) == 0.  Returns the
+    two tables as int64 tensors (host or device, as given) and (B, S, M, C, Q, L, P)."""
+    ss = spatial_shapes if isinstance(spatial_shapes, torch.Tensor) else torch.as_tensor(spatial_shapes)
+    ls = level_start_index if isinstance(level_start_index, torch.Tensor) else torch.as_tensor(level_start_index)
+    floats = (value, sampling_loc, attn_weight, *grads)
+    if value.dtype not in _MSDA_DTYPE:
+        raise ValueError(f"ms_deform_attn: value must be float32 or float64, got {value.dtype}")
+    if any(t.dtype != value.dtype for t in floats):
+        raise ValueError("ms_deform_attn: value, sampling_loc, attn_weight (and grad_output) must share one dtype, got "
+                         + ", ".join(str(t.dtype) for t in floats))
+    if ss.dtype != torch.int64 or ls.dtype != torch.int64:
+        raise ValueError(f"ms_deform_attn: spatial_shapes / level_start_index must be int64, got {ss.dtype} / {ls.dtype}")
+    if not all(t.is_cuda for t in floats):
+        raise ValueError("ms_deform_attn: value, sampling_loc, attn_weight must be GPU tensors (no CPU path)")
+    if not all(t.is_contiguous() for t in (*floats, ss, ls)):
+        raise ValueError("ms_deform_attn: every tensor must be contiguous")
+    if value.dim() != 4 or sampling_loc.dim() != 6 or sampling_loc.shape[-1] != 2:
+        raise ValueError("ms_deform_attn: value must be [B,S,M,C] and sampling_loc [B,Q,M,L,P,2]")
+    B, S, M, Cn = value.shape
+    _, Q, _, L, P, _ = sampling_loc.shape
+    if (tuple(sampling_loc.shape[:3]) != (B, Q, M) or tuple(attn_weight.shape) != (B, Q, M, L, P)
+            or tuple(ss.shape) != (L, 2) or tuple(ls.shape) != (L,)):
+        raise ValueError("ms_deform_attn: inconsistent shapes of value / spatial_shapes / level_start_index / "
+                         "sampling_loc / attn_weight")
+    if any(tuple(g.shape) != (B, Q, M * Cn) for g in grads):
+        raise ValueError(f"ms_deform_attn: grad_output must be [B,Q,M*C] = {(B, Q, M * Cn)}")
+    step = min(B, im2col_step)
+    if im2col_step <= 0 or B % step != 0:
+        raise ValueError(f"ms_deform_attn: im2col_step ({im2col_step}) must divide batch ({B})")
+    for t, name in ((ss, "spatial_shapes"), (ls, "level_start_index")):
+        if t.is_cuda and t.device != value.device:
+            raise ValueError(f"ms_deform_attn: {name} is on {t.device}, value on {value.device}")
+    return ss, ls, (B, S, M, Cn, Q, L, P)
+
+
+def _msda_device_tables(ss: torch.Tensor, ls: torch.Tensor, S: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device copies of host tables (checked here first: on the host that costs nothing); device tables as given -
+    reading them would synchronise, so the kernels bound every row they touch instead (include/inklayer_hip.h)."""
+    if ss.is_cuda and ls.is_cuda:
+        return ss, ls
+    if ss.is_cuda or ls.is_cuda:
+        raise ValueError("ms_deform_attn: spatial_shapes and level_start_index must both be host or both be device tensors")
+    hw = [int(h) * int(w) for h, w in ss.tolist()]
+    starts = [sum(hw[:i]) for i in range(len(hw))]
+    if min(int(v) for v in ss.reshape(-1).tolist()) <= 0 or sum(hw) != S or ls.tolist() != starts:
+        raise ValueError(f"ms_deform_attn: spatial_shapes {ss.tolist()} / level_start_index {ls.tolist()} do not "
+                         f"describe the {S} rows of value")
+    return ss.to(dev), ls.to(dev)
+
+
 def ms_deform_attn_forward(value: torch.Tensor, spatial_shapes, level_start_index,
                            sampling_loc: torch.Tensor, attn_weight: torch.Tensor,
                            im2col_step: int = 64) -> torch.Tensor:
-    """Same argument list as groundingdino._C.ms_deform_attn_forward (GD/.../csrc/vision.cpp:53-56)."""
-    assert value.dtype == F32 and value.is_contiguous() and value.is_cuda
-    assert sampling_loc.dtype == F32 and sampling_loc.is_contiguous()
-    assert attn_weight.dtype == F32 and attn_weight.is_contiguous()
-    B, S, M, Cn = value.shape
-    _, Q, _, L, P, _ = sampling_loc.shape
-    ss = [int(v) for v in torch.as_tensor(spatial_shapes).reshape(-1).tolist()]
-    ls = [int(v) for v in torch.as_tensor(level_start_index).reshape(-1).tolist()]
-    out = torch.empty((B, Q, M * Cn), device=value.device, dtype=F32)
-    check(_lib.lib().ink_ms_deform_attn_forward(
-        value.data_ptr(), (C.c_int64 * len(ss))(*ss), (C.c_int64 * len(ls))(*ls), sampling_loc.data_ptr(),
-        attn_weight.data_ptr(), B, S, M, Cn, Q, L, P, im2col_step, out.data_ptr(), _stream()),
-        "ink_ms_deform_attn_forward")
+    """Same argument list and semantics as groundingdino._C.ms_deform_attn_forward (GD/.../csrc/vision.cpp:54):
+    value [B,S,M,C], spatial_shapes int64 [L,2], level_start_index int64 [L], sampling_loc [B,Q,M,L,P,2],
+    attn_weight [B,Q,M,L,P] -> [B,Q,M*C], f32 or f64, any C and L.  Device shape tables are passed to the kernel
+    as they are (no host synchronisation); host tables of the f32 / C == 32 / L <= 8 form take the host-table
+    entry point (the same kernel: the same bits), other host tables are copied to the device."""
+    ss, ls, (B, S, M, Cn, Q, L, P) = _msda_check(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                 im2col_step)
+    out = torch.empty((B, Q, M * Cn), device=value.device, dtype=value.dtype)
+    if not ss.is_cuda and not ls.is_cuda and value.dtype == F32 and Cn == 32 and L <= 8:
+        sl = [int(v) for v in ss.reshape(-1).tolist()]
+        ll = [int(v) for v in ls.tolist()]
+        check(_lib.lib().ink_ms_deform_attn_forward(
+            value.data_ptr(), (C.c_int64 * len(sl))(*sl), (C.c_int64 * len(ll))(*ll), sampling_loc.data_ptr(),
+            attn_weight.data_ptr(), B, S, M, Cn, Q, L, P, im2col_step, out.data_ptr(), _stream()),
+            "ink_ms_deform_attn_forward")
+        return out
+    ss, ls = _msda_device_tables(ss, ls, S, value.device)
+    check(_lib.lib().ink_ms_deform_attn_forward_dev(
+        value.data_ptr(), ss.data_ptr(), ls.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+        _MSDA_DTYPE[value.dtype], B, S, M, Cn, Q, L, P, im2col_step, out.data_ptr(), _stream()),
+        "ink_ms_deform_attn_forward_dev")
     return out
+
+
+def ms_deform_attn_backward(value: torch.Tensor, spatial_shapes, level_start_index, sampling_loc: torch.Tensor,
+                            attn_weight: torch.Tensor, grad_output: torch.Tensor, im2col_step: int = 64):
+    """Same argument list and results as groundingdino._C.ms_deform_attn_backward (GD/.../csrc/vision.cpp:55):
+    returns (grad_value, grad_sampling_loc, grad_attn_weight), each with its input's shape and dtype.  grad_value
+    is summed with float atomics, so its last bits vary from run to run (as the reference's do)."""
+    ss, ls, (B, S, M, Cn, Q, L, P) = _msda_check(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                                 im2col_step, grad_output)
+    ss, ls = _msda_device_tables(ss, ls, S, value.device)
+    grad_value = torch.empty_like(value)                 # zeroed by the entry point on the stream
+    grad_loc = torch.empty_like(sampling_loc)
+    grad_aw = torch.empty_like(attn_weight)
+    check(_lib.lib().ink_ms_deform_attn_backward_dev(
+        value.data_ptr(), ss.data_ptr(), ls.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+        grad_output.data_ptr(), _MSDA_DTYPE[value.dtype], B, S, M, Cn, Q, L, P, im2col_step, grad_value.data_ptr(),
+        grad_loc.data_ptr(), grad_aw.data_ptr(), _stream()), "ink_ms_deform_attn_backward_dev")
+    return grad_value, grad_loc, grad_aw
+
+
+class _MSDeformAttnFunction(torch.autograd.Function):
+    """Differentiable form (MultiScaleDeformableAttnFunction, GD/models/GroundingDINO/ms_deform_attn.py:45-90):
+    once-differentiable, gradients for value, sampling_loc and attn_weight."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
+        ctx.im2col_step = im2col_step
+        ctx.save_for_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+        return ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        value, spatial_shapes, level_start_index, sampling_loc, attn_weight = ctx.saved_tensors
+        gv, gl, ga = ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                             grad_output.contiguous(), ctx.im2col_step)
+        return gv, None, None, gl, ga, None
+
+
+def ms_deform_attn(value: torch.Tensor, spatial_shapes, level_start_index, sampling_loc: torch.Tensor,
+                   attn_weight: torch.Tensor, im2col_step: int = 64) -> torch.Tensor:
+    """Differentiable multi-scale deformable attention: ms_deform_attn_forward with a backward through
+    ms_deform_attn_backward (for value, sampling_loc and attn_weight)."""
+    ss = spatial_shapes if isinstance(spatial_shapes, torch.Tensor) else torch.as_tensor(spatial_shapes)
+    ls = level_start_index if isinstance(level_start_index, torch.Tensor) else torch.as_tensor(level_start_index)
+    return _MSDeformAttnFunction.apply(value, ss, ls, sampling_loc, attn_weight, im2col_step)
 
 
 def msda_fused(value16: torch.Tensor, proj: torch.Tensor, ref: torch.Tensor, shapes: Sequence[Tuple[int, int]],
