@@ -222,6 +222,30 @@ int ink_im2col3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32
 int ink_sam_pe_encode(const float* coords01, const float* gauss, int32_t N, int32_t F,
                       const float* add, int32_t n_add, float* out, void* stream);
 
+/* The whole token block of the SAM mask decoder for P prompts (SA/modeling/prompt_encoder.py:73-100, 128-166;
+ * mask_decoder.py:113-116): out f32 [P, NT, 2F], NT = 5 + n_pts + pad + 2 * (boxes != NULL) <= 16, holds the 5 output
+ * tokens (out_tok f32 [5, 2F]: iou token + 4 mask tokens), then the point tokens, then the two box corners.  points f32
+ * [P, n_pts, 2] (x, y) and boxes f32 [P, 4] (xyxy) are in the resized-input frame: they are shifted by +0.5 and divided
+ * by input_size here.  labels int32 [P, n_pts]; pad = 1 appends the point (0, 0) with label -1 (the reference pads when
+ * there is no box).  Label -1: not_a_point (f32 [2F]) in place of the positional encoding; 0 / 1: the encoding +
+ * point_emb[label]; any other label: the encoding alone.  point_emb f32 [4, 2F] = point_embeddings 0..3 (negative,
+ * positive, box corner 0, box corner 1).  A box-only block equals ink_sam_pe_encode(.., add = point_emb + 2F, n_add 2)
+ * behind the 5 output tokens, bit for bit. */
+int ink_sam_prompt_tokens(const float* points, const int32_t* labels, int32_t n_pts, int32_t pad, const float* boxes,
+                          const float* gauss, int32_t F, const float* point_emb, const float* not_a_point,
+                          const float* out_tok, float input_size, int32_t P, float* out, void* stream);
+
+/* Mask prompt (PromptEncoder.mask_downscaling, prompt_encoder.py:50-59) added to the image embedding
+ * (mask_decoder.py:123-126), fused: keys f32 [P*g*g, 256], keys[p*g*g + t] = emb[emb_rows[p] + t] + dense(mask[p])[t]
+ * with dense = Conv1x1(16 -> 256)(GELU(LN2d(Conv2x2s2(4 -> 16)(GELU(LN2d(Conv2x2s2(1 -> 4)(mask))))))).  mask f32
+ * [P, 1, 4g, 4g] logits (g <= 64), emb f32 [*, 256] token rows, emb_rows int32 [P].  params f32 [4684] = the layers'
+ * tensors flattened in order: conv1 w [4,1,2,2], b [4], LN w [4], b [4], conv2 w [16,4,2,2], b [16], LN w [16], b [16],
+ * conv3 w [256,16,1,1], b [256]; n_params must be 4684.  eps: the LayerNorm2d epsilon (1e-6).  split_f16 (f16 [P*g*g, 768]
+ * or NULL) receives the split-f16 GEMM operand of keys (see ink_add_split_f16) in the same pass.  16-byte aligned
+ * mask / emb / keys. */
+int ink_sam_mask_embed(const float* mask, const float* emb, const int32_t* emb_rows, const float* params,
+                       int32_t n_params, float eps, int32_t P, int32_t g, float* keys, void* split_f16, void* stream);
+
 /* masks = hyper_in @ upscaled_embedding for ONE mask token (SA/modeling/mask_decoder.py:139-144),
  * reading the ConvTranspose output in its un-shuffled GEMM layout
  * up[((b*g*g + y*g + x)*4 + (dy1*2+dx1))*4 + (dy2*2+dx2), C] and writing the pixel-shuffled
@@ -339,11 +363,11 @@ int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
                      const uint8_t* blocked, const int32_t* q_batch_rows, const float* q_add, int32_t io_f32, void* O,
                      int64_t ldo, void* stream);
 
-/* softmax(scale q k^T) v for n_q <= 8 queries per batch entry against MANY keys (SAM decoder tokens ->
- * image: 7 x 4096, SA/modeling/transformer.py:163-168): head h at columns [h*hd,(h+1)*hd),
+/* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
+ * image: 7..16 x 4096, SA/modeling/transformer.py:163-168): head h at columns [h*hd,(h+1)*hd),
  * hd in {16,32}; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].  io_f32 = 0: f16 rows,
- * 1: f32 rows (head_dim 16 with n_heads % 4 == 0 only).  k_add (f32 [n_k, n_heads*hd] or NULL, f32 rows only) is
- * added to the key rows by key position. */
+ * 1: f32 rows (head_dim 16 with n_heads % 4 == 0 only).  n_q > 8 needs f32 rows.  k_add (f32 [n_k, n_heads*hd] or
+ * NULL, f32 rows only) is added to the key rows by key position. */
 int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                   int32_t n_batch, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale,
                   const int32_t* q_batch_rows, const int32_t* kv_batch_rows, const float* k_add, int32_t io_f32, void* O,
@@ -378,6 +402,11 @@ int ink_fusion_fold(float* v_f32, int32_t B, int32_t S, const float* lnv_g, cons
 int ink_sam_upscale_pack(const void* ws_f16, void* blob_f16, void* stream);
 int ink_sam_upscale_tail(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const float* ln_g, const float* ln_b, float eps,
                          const void* blob_f16, const float* b3, const float* hyper, float* low, void* stream);
+/* The same for n_masks in {1, 3, 4} mask tokens per box (multimask output): hyper f32 [n, n_masks, 32], low f32
+ * [n, n_masks, 4g, 4g].  Mask 0 of a 4-mask call equals ink_sam_upscale_tail bit for bit; n_masks = 1 is that call. */
+int ink_sam_upscale_tail_masks(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const float* ln_g,
+                               const float* ln_b, float eps, const void* blob_f16, const float* b3, const float* hyper,
+                               int32_t n_masks, float* low, void* stream);
 
 /* Image-side tail of a layer of SAM's two-way transformer in one kernel (csrc/proj_ln.hip):
  *     out = LayerNorm(res + a W^T + bias)         a f32 [rows, 128] (the image->token attention's output), 256 columns

@@ -63,6 +63,10 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "ink_sam_pe_encode": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "ink_sam_mask_logits": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_sam_prompt_tokens": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p, c_float, c_int, c_void_p, c_void_p],
+    "ink_sam_mask_embed": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                           c_void_p],
     "ink_sam_postprocess": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                             c_void_p, c_void_p, c_void_p],
     "ink_ms_deform_attn_forward": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), c_void_p, c_void_p, c_int,
@@ -92,6 +96,8 @@ SIGNATURES = {
     "ink_sam_upscale_pack": [c_void_p, c_void_p, c_void_p],
     "ink_sam_upscale_tail": [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p],
+    "ink_sam_upscale_tail_masks": [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_void_p, c_void_p],
     "ink_ffn256_pack_bytes": [c_int, c_int, C.POINTER(c_i64)],
     "ink_ffn256_pack": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "ink_ffn256_fused": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,

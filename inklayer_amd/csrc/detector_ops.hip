@@ -756,6 +756,198 @@ __global__ __launch_bounds__(256 * KSPLIT) void attn_fewq16_kernel(const T* __re
   }
 }
 
+// Same scheme for 9..16 queries (SAM point prompts: up to 16 tokens), f32 rows: wave w owns queries QW w .. QW w + QW - 1,
+// so the K / V tiles are still staged once per workgroup for all queries.  The scaled queries live in LDS (read as
+// broadcasts per tile) rather than in registers: with QW = 4, 64 query registers on top of the 64 accumulators and the
+// tile prefetch spill at two waves per SIMD.  The per-query arithmetic (score order, one rescale per tile, merges, fold)
+// is that of attn_fewq16_kernel, so a query gets the same bits from either kernel.
+template <int QW, int KSPLIT>
+__global__ __launch_bounds__(256 * KSPLIT) void attn_fewq16_wide_kernel(const float* __restrict__ Q, int64_t ldq,
+                                                                        const float* __restrict__ K, int64_t ldk,
+                                                                        const float* __restrict__ V, int64_t ldv,
+                                                                        int n_q, int n_k, int n_heads, float scale,
+                                                                        const int32_t* __restrict__ q_rows,
+                                                                        const int32_t* __restrict__ kv_rows,
+                                                                        const float* __restrict__ k_add,
+                                                                        float* __restrict__ O, int64_t ldo) {
+  constexpr int HD = 16, HB = 4, TK = 64;
+  constexpr int ROWE = HB * HD;
+  constexpr int CH = 4, NCH = ROWE / CH, NU = TK * NCH / 256;
+  extern __shared__ __attribute__((aligned(16))) char fewq_smem[];
+  const int grp = threadIdx.x >> 8;
+  float* sk = (float*)fewq_smem + grp * 2 * TK * ROWE;
+  float* sv = sk + TK * ROWE;
+  const int hgroups = n_heads / HB;
+  const int b = blockIdx.x / hgroups, h0 = (blockIdx.x % hgroups) * HB;
+  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+  const int per = ((n_k + KSPLIT - 1) / KSPLIT + TK - 1) / TK * TK;
+  const int k_lo = grp * per, k_hi = min(n_k, k_lo + per);
+  const int kl = lane >> 2, hl = lane & 3;
+  const int64_t q0 = q_rows ? (int64_t)q_rows[b] : (int64_t)b * n_q;
+  const int64_t k0 = kv_rows ? (int64_t)kv_rows[b] : (int64_t)b * n_k;
+  float* sq = (float*)fewq_smem + KSPLIT * 2 * TK * ROWE;     // [4 QW queries][4 heads][16], written by group 0
+  if (grp == 0 && kl == 0) {
+    const float sc2 = scale * 1.44269504088896340736f;
+#pragma unroll
+    for (int j = 0; j < QW; ++j) {
+      const int qi = QW * wave + j;
+      const float* pq = Q + (q0 + (qi < n_q ? qi : 0)) * ldq + (h0 + hl) * HD;
+      float qf[HD];
+      load8(pq, qf);
+      load8(pq + 8, qf + 8);
+#pragma unroll
+      for (int e = 0; e < HD; ++e) qf[e] *= sc2;
+      store8(sq + (qi * HB + hl) * HD, qf);
+      store8(sq + (qi * HB + hl) * HD + 8, qf + 8);
+    }
+  }                                                  // visible after the first tile's barrier
+  float m[QW], l[QW], acc[QW][HD];
+#pragma unroll
+  for (int j = 0; j < QW; ++j) {
+    m[j] = -3.0e38f;
+    l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < HD; ++i) acc[j][i] = 0.f;
+  }
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 rk[NU], rv[NU];
+  auto fetch = [&](int t0) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int c = tid + 256 * u, row = c / NCH, col = c % NCH;
+      rk[u] = rv[u] = (u32x4){0u, 0u, 0u, 0u};
+      if (t0 + row < k_hi) {
+        rk[u] = *(const u32x4*)(K + (k0 + t0 + row) * ldk + h0 * HD + col * CH);
+        rv[u] = *(const u32x4*)(V + (k0 + t0 + row) * ldv + h0 * HD + col * CH);
+        if (k_add) {
+          const f32x4 ad = *(const f32x4*)(k_add + (int64_t)(t0 + row) * n_heads * HD + h0 * HD + col * CH);
+          f32x4 kv4 = __builtin_bit_cast(f32x4, rk[u]);
+          kv4 += ad;
+          rk[u] = __builtin_bit_cast(u32x4, kv4);
+        }
+      }
+    }
+  };
+  fetch(k_lo);
+  for (int t0 = k_lo; t0 < k_lo + per; t0 += TK) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int c = tid + 256 * u, row = c / NCH, col = c % NCH;
+      *(u32x4*)(sk + row * ROWE + col * CH) = rk[u];
+      *(u32x4*)(sv + row * ROWE + col * CH) = rv[u];
+    }
+    __syncthreads();
+    if (t0 + TK < k_hi) fetch(t0 + TK);
+    float d[QW][TK / 16];
+#pragma unroll
+    for (int kk = 0; kk < TK / 16; ++kk) {
+      const int key = kk * 16 + kl;
+      float kf[HD];
+      load8(sk + key * ROWE + hl * HD, kf);
+      load8(sk + key * ROWE + hl * HD + 8, kf + 8);
+      const bool in = t0 + key < k_hi;
+#pragma unroll
+      for (int j = 0; j < QW; ++j) {
+        float qf[HD];
+        load8(sq + ((QW * wave + j) * HB + hl) * HD, qf);
+        load8(sq + ((QW * wave + j) * HB + hl) * HD + 8, qf + 8);
+        float a0 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          a0 = fmaf(qf[e], kf[e], a0);
+          a0 = fmaf(qf[8 + e], kf[8 + e], a0);
+        }
+        d[j][kk] = in ? a0 : -3.0e38f;
+      }
+    }
+    float n[QW];
+#pragma unroll
+    for (int j = 0; j < QW; ++j) {
+      n[j] = m[j];
+#pragma unroll
+      for (int kk = 0; kk < TK / 16; ++kk) n[j] = fmaxf(n[j], d[j][kk]);
+      const float sj = __builtin_amdgcn_exp2f(m[j] - n[j]);
+      l[j] *= sj;
+#pragma unroll
+      for (int e = 0; e < HD; ++e) acc[j][e] *= sj;
+      m[j] = n[j];
+    }
+#pragma unroll
+    for (int kk = 0; kk < TK / 16; ++kk) {
+      const int key = kk * 16 + kl;
+      float vf[HD];
+      load8(sv + key * ROWE + hl * HD, vf);
+      load8(sv + key * ROWE + hl * HD + 8, vf + 8);
+      const bool in = t0 + key < k_hi;
+#pragma unroll
+      for (int j = 0; j < QW; ++j) {
+        const float pj = in ? __builtin_amdgcn_exp2f(d[j][kk] - n[j]) : 0.f;
+        l[j] += pj;
+#pragma unroll
+        for (int e = 0; e < HD; ++e) acc[j][e] = fmaf(pj, vf[e], acc[j][e]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < QW; ++j) {
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {               // the 16 key-lanes of this head: lane bits 2..5
+      const float mo = __shfl_xor(m[j], o, 64), lo = __shfl_xor(l[j], o, 64);
+      const float mn = fmaxf(m[j], mo);
+      const float a = __builtin_amdgcn_exp2f(m[j] - mn), bsc = __builtin_amdgcn_exp2f(mo - mn);
+      l[j] = l[j] * a + lo * bsc;
+#pragma unroll
+      for (int i = 0; i < HD; ++i) acc[j][i] = acc[j][i] * a + __shfl_xor(acc[j][i], o, 64) * bsc;
+      m[j] = mn;
+    }
+  }
+  if constexpr (KSPLIT > 1) {
+    __syncthreads();
+    float* st = (float*)fewq_smem;
+    if (grp > 0 && kl == 0) {
+#pragma unroll
+      for (int j = 0; j < QW; ++j) {
+        float* ps = st + ((((grp - 1) * 4 + wave) * QW + j) * 4 + hl) * 18;
+        ps[0] = m[j];
+        ps[1] = l[j];
+#pragma unroll
+        for (int i = 0; i < HD; ++i) ps[2 + i] = acc[j][i];
+      }
+    }
+    __syncthreads();
+    if (grp > 0) return;
+    if (kl == 0) {
+#pragma unroll
+      for (int g2 = 1; g2 < KSPLIT; ++g2)
+#pragma unroll
+        for (int j = 0; j < QW; ++j) {
+          const float* ps = st + ((((g2 - 1) * 4 + wave) * QW + j) * 4 + hl) * 18;
+          const float mo = ps[0], mn = fmaxf(m[j], mo);
+          const float a = __builtin_amdgcn_exp2f(m[j] - mn), bsc = __builtin_amdgcn_exp2f(mo - mn);
+          l[j] = l[j] * a + ps[1] * bsc;
+#pragma unroll
+          for (int i = 0; i < HD; ++i) acc[j][i] = acc[j][i] * a + ps[2 + i] * bsc;
+          m[j] = mn;
+        }
+    }
+  }
+  if (kl == 0) {
+#pragma unroll
+    for (int j = 0; j < QW; ++j) {
+      const int qi = QW * wave + j;
+      if (qi < n_q) {
+        const float inv = 1.f / l[j];
+#pragma unroll
+        for (int i = 0; i < HD; ++i) acc[j][i] *= inv;
+        float* op = O + ((int64_t)b * n_q + qi) * ldo + (h0 + hl) * HD;
+        store8(op, acc[j]);
+        store8(op + 8, acc[j] + 8);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Two-stage query selection: key[s] = max_t logits[b,s,t]; indices of the K largest, in descending
 // order, ties -> lower index (torch.topk leaves tie order unspecified).  One 1024-thread workgroup
@@ -968,11 +1160,18 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
   else if (head_dim == 64 && !io_f32) INK_FEWKEYS(64, f16);
   else if (head_dim == 16 && !io_f32) INK_FEWKEYS(16, f16);
   else if (head_dim == 32) INK_FEWKEYS(32, float);
-  else if (head_dim == 16 && !blocked && n_k == 7) {        // SAM's 5 output tokens + 2 box corners
-    const int64_t t4 = total * 4;
-    hipLaunchKernelGGL(attn_fewkeys16_f32_kernel<7>, dim3((unsigned)((t4 + 255) / 256)), block, 0, s, (const float*)Q, ldq,
-                       (const float*)K, ldk, (const float*)V, ldv, B, n_q, n_heads, scale, q_batch_rows, q_add,
-                       (float*)O, ldo);
+  else if (head_dim == 16 && !blocked && n_k >= 7) {        // SAM's 5 output tokens + 2..11 prompt tokens
+    const dim3 g4((unsigned)((total * 4 + 255) / 256));
+#define INK_FEWKEYS16(NK)                                                                                        \
+  case NK:                                                                                                      \
+    hipLaunchKernelGGL(attn_fewkeys16_f32_kernel<NK>, g4, block, 0, s, (const float*)Q, ldq, (const float*)K, ldk, \
+                       (const float*)V, ldv, B, n_q, n_heads, scale, q_batch_rows, q_add, (float*)O, ldo);         \
+    break
+    switch (n_k) {
+      INK_FEWKEYS16(7); INK_FEWKEYS16(8); INK_FEWKEYS16(9); INK_FEWKEYS16(10); INK_FEWKEYS16(11);
+      INK_FEWKEYS16(12); INK_FEWKEYS16(13); INK_FEWKEYS16(14); INK_FEWKEYS16(15); INK_FEWKEYS16(16);
+    }
+#undef INK_FEWKEYS16
   } else if (head_dim == 16) INK_FEWKEYS(16, float);
   else return INK_ERR_ARG;
 #undef INK_FEWKEYS
@@ -983,13 +1182,22 @@ extern "C" int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t 
                              int32_t n_batch, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim,
                              float scale, const int32_t* q_batch_rows, const int32_t* kv_batch_rows,
                              const float* k_add, int32_t io_f32, void* O, int64_t ldo, void* stream) {
-  INK_CHECK_ARG(Q && K && V && O && n_batch > 0 && n_q > 0 && n_q <= 8 && n_k > 0 && n_heads > 0);
+  INK_CHECK_ARG(Q && K && V && O && n_batch > 0 && n_q > 0 && n_q <= 16 && n_k > 0 && n_heads > 0);
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
   INK_CHECK_ARG(io_f32 == 0 || (io_f32 == 1 && head_dim == 16 && n_heads % 4 == 0));
   INK_CHECK_ARG(!k_add || (io_f32 == 1 && ((uintptr_t)k_add & 15) == 0));
+  INK_CHECK_ARG(n_q <= 8 || io_f32 == 1);             // 9..16 queries: the f32 4-queries-per-wave form only
   const dim3 grid(n_batch * n_heads), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (head_dim == 16 && n_heads % 4 == 0 && io_f32) {
+  if (n_q > 8) {
+    constexpr int lds = 2 * 2 * 64 * 64 * 4 + 16 * 64 * 4;   // the K / V tiles as below + the scaled queries
+    static bool attr = ((void)hipFuncSetAttribute((const void*)attn_fewq16_wide_kernel<4, 2>,
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
+    (void)attr;
+    hipLaunchKernelGGL((attn_fewq16_wide_kernel<4, 2>), dim3(n_batch * (n_heads / 4)), dim3(512), lds, s, (const float*)Q,
+                       ldq, (const float*)K, ldk, (const float*)V, ldv, n_q, n_k, n_heads, scale, q_batch_rows,
+                       kv_batch_rows, k_add, (float*)O, ldo);
+  } else if (head_dim == 16 && n_heads % 4 == 0 && io_f32) {
     constexpr int lds = 2 * 2 * 64 * 64 * 4;           // two key-range groups x (K, V) tiles of 64 keys x 4 heads x 16 f32
     static bool attr = ((void)hipFuncSetAttribute((const void*)attn_fewq16_kernel<float, 2>,
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);

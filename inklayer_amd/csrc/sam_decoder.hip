@@ -4,6 +4,16 @@
 
 namespace {
 
+// Feature f of PositionEmbeddingRandom._pe_encoding at a point (x, y) in [0, 1]^2: sin / cos(2*pi*((2c-1) @ G[:, f]))
+__device__ __forceinline__ void pe_feature(float x, float y, const float* __restrict__ G, int F, int f, float& sv,
+                                           float& cv) {
+  const float cx = 2.f * x - 1.f, cy = 2.f * y - 1.f;
+  float v = cx * G[f] + cy * G[F + f];
+  v = 6.283185307179586f * v;
+  sv = sinf(v);
+  cv = cosf(v);
+}
+
 // PositionEmbeddingRandom._pe_encoding: out = [sin(2*pi*((2c-1) @ G)), cos(..)]
 __global__ __launch_bounds__(256) void pe_encode_kernel(const float* __restrict__ coords,
                                                         const float* __restrict__ G, int N, int F,
@@ -12,10 +22,8 @@ __global__ __launch_bounds__(256) void pe_encode_kernel(const float* __restrict_
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N * F) return;
   const int n = i / F, f = i % F;
-  const float cx = 2.f * coords[2 * n] - 1.f, cy = 2.f * coords[2 * n + 1] - 1.f;
-  float v = cx * G[f] + cy * G[F + f];
-  v = 6.283185307179586f * v;
-  float sv = sinf(v), cv = cosf(v);
+  float sv, cv;
+  pe_feature(coords[2 * n], coords[2 * n + 1], G, F, f, sv, cv);
   if (add) {
     const float* ar = add + (int64_t)(n % n_add) * 2 * F;
     sv += ar[f];
@@ -23,6 +31,174 @@ __global__ __launch_bounds__(256) void pe_encode_kernel(const float* __restrict_
   }
   out[(int64_t)n * 2 * F + f] = sv;
   out[(int64_t)n * 2 * F + F + f] = cv;
+}
+
+// The whole token block of P prompts, [P, NT, 2F] with NT = 5 + n_pts + pad + 2 * (boxes != null): the 5 output tokens
+// (iou + 4 mask tokens, copied), then PromptEncoder._embed_points and _embed_boxes (SA/modeling/prompt_encoder.py:73-100,
+// 128-166).  Points and boxes are in the resized-input frame; the +0.5 pixel-centre shift and the division by the input
+// size happen here in f32, as the reference does them.  The pad point (0, 0) is appended after the shift, unshifted.
+// Label -1: not_a_point_embed in place of the positional encoding; 0 / 1: PE + point_embeddings[label]; any other
+// label: the PE alone.  pemb = point_embeddings[0..3] ([4, 2F]: negative, positive, box corner 0, box corner 1).
+__global__ __launch_bounds__(256) void prompt_tokens_kernel(const float* __restrict__ points,
+                                                            const int32_t* __restrict__ labels, int n_pts, int pad,
+                                                            const float* __restrict__ boxes, const float* __restrict__ G,
+                                                            int F, const float* __restrict__ pemb,
+                                                            const float* __restrict__ nap,
+                                                            const float* __restrict__ out_tok, float size, int P, int NT,
+                                                            float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)P * NT * F) return;
+  const int f = (int)(i % F), t = (int)((i / F) % NT);
+  const int64_t p = i / ((int64_t)F * NT);
+  float* o = out + (p * NT + t) * 2 * F;
+  if (t < 5) {
+    o[f] = out_tok[t * 2 * F + f];
+    o[F + f] = out_tok[t * 2 * F + F + f];
+    return;
+  }
+  const int s = t - 5;
+  float x, y;
+  const float* add;
+  if (s < n_pts + pad) {
+    int lab = -1;
+    x = y = 0.f;
+    if (s < n_pts) {
+      lab = labels[p * n_pts + s];
+      x = (points[(p * n_pts + s) * 2] + 0.5f) / size;
+      y = (points[(p * n_pts + s) * 2 + 1] + 0.5f) / size;
+    }
+    if (lab == -1) {                 // point_embedding[labels == -1] = 0; += not_a_point_embed
+      o[f] = 0.f + nap[f];
+      o[F + f] = 0.f + nap[F + f];
+      return;
+    }
+    add = (lab == 0 || lab == 1) ? pemb + lab * 2 * F : nullptr;
+  } else {
+    const int c = s - n_pts - pad;   // box corner 0 / 1
+    x = (boxes[p * 4 + 2 * c] + 0.5f) / size;
+    y = (boxes[p * 4 + 2 * c + 1] + 0.5f) / size;
+    add = pemb + (2 + c) * 2 * F;
+  }
+  float sv, cv;
+  pe_feature(x, y, G, F, f, sv, cv);
+  if (add) {
+    sv += add[f];
+    cv += add[F + f];
+  }
+  o[f] = sv;
+  o[F + f] = cv;
+}
+
+// PromptEncoder.mask_downscaling (prompt_encoder.py:50-59) + the image embedding it is added to (mask_decoder.py:123-126),
+// for E = 256 and mask_in_chans = 16: keys[p*g*g + tok] = emb[emb_rows[p] + tok] + Conv1x1(GELU(LN2d(Conv2x2(GELU(LN2d(
+// Conv2x2(mask[p])))))))[tok].  Output token (y, x) depends on the 4x4 input patch at (4y, 4x) only.  One workgroup per
+// (prompt, token row y): lanes 0..g-1 run the two tiny convolutions of one token each in registers (f32) and park the 16
+// channels in LDS; then every wave writes whole 1-KiB output rows (lane = 4 channels of the 16 -> 256 projection, whose
+// weights stay in registers).  Optionally the split-f16 GEMM operand of the keys ([hi | lo*64 | hi/64], ink_add_split_f16)
+// is written in the same pass.
+// prm (f32): conv1 w [4][2][2], b [4], ln1 w [4], b [4], conv2 w [16][4][2][2], b [16], ln2 w [16], b [16],
+//            conv3 w [256][16], b [256]
+constexpr int ME = 256, MC = 16, MC1 = MC / 4;
+constexpr int MP_W1 = 0, MP_B1 = 16, MP_G1 = 20, MP_BE1 = 24, MP_W2 = 28, MP_B2 = 284, MP_G2 = 300, MP_BE2 = 316,
+              MP_W3 = 332, MP_B3 = 332 + ME * MC, MP_TOTAL = MP_B3 + ME;
+
+__global__ __launch_bounds__(256) void mask_embed_kernel(const float* __restrict__ mask, const float* __restrict__ emb,
+                                                         const int32_t* __restrict__ emb_rows,
+                                                         const float* __restrict__ prm, float eps, int g,
+                                                         float* __restrict__ keys, f16* __restrict__ split) {
+  __shared__ float s_h[64 * MC];
+  const int p = blockIdx.x / g, y = blockIdx.x % g, tid = threadIdx.x;
+  const int S = 4 * g;                                   // mask side
+  if (tid < g) {
+    const int x = tid;
+    const float* mp = mask + ((int64_t)p * S + 4 * y) * S + 4 * x;
+    f32x4 m[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m[r] = *(const f32x4*)(mp + (int64_t)r * S);
+    float h1[MC1][2][2];                                 // conv1 -> LayerNorm2d(4) -> GELU at the 2x2 positions
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float c[MC1], mu = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < MC1; ++ch) {
+          const float* w = prm + MP_W1 + ch * 4;
+          float a = prm[MP_B1 + ch];
+          a = fmaf(w[0], m[2 * i][2 * j], a);
+          a = fmaf(w[1], m[2 * i][2 * j + 1], a);
+          a = fmaf(w[2], m[2 * i + 1][2 * j], a);
+          a = fmaf(w[3], m[2 * i + 1][2 * j + 1], a);
+          c[ch] = a;
+          mu += a;
+        }
+        mu *= 1.f / MC1;
+        float var = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < MC1; ++ch) var += (c[ch] - mu) * (c[ch] - mu);
+        const float rs = 1.f / sqrtf(var * (1.f / MC1) + eps);
+#pragma unroll
+        for (int ch = 0; ch < MC1; ++ch)
+          h1[ch][i][j] = gelu_erf(prm[MP_G1 + ch] * ((c[ch] - mu) * rs) + prm[MP_BE1 + ch]);
+      }
+    float c2[MC], mu = 0.f;                              // conv2 -> LayerNorm2d(16) -> GELU
+#pragma unroll
+    for (int o = 0; o < MC; ++o) {
+      const float* w = prm + MP_W2 + o * MC1 * 4;
+      float a = prm[MP_B2 + o];
+#pragma unroll
+      for (int ch = 0; ch < MC1; ++ch)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a = fmaf(w[ch * 4 + k], h1[ch][k >> 1][k & 1], a);
+      c2[o] = a;
+      mu += a;
+    }
+    mu *= 1.f / MC;
+    float var = 0.f;
+#pragma unroll
+    for (int o = 0; o < MC; ++o) var += (c2[o] - mu) * (c2[o] - mu);
+    const float rs = 1.f / sqrtf(var * (1.f / MC) + eps);
+#pragma unroll
+    for (int o = 0; o < MC; ++o) s_h[x * MC + o] = gelu_erf(prm[MP_G2 + o] * ((c2[o] - mu) * rs) + prm[MP_BE2 + o]);
+  }
+  __syncthreads();
+  // conv3 (1x1, 16 -> 256) + the image embedding: lane = channels 4 c4 .. 4 c4 + 3, wave w = tokens w, w + 4, ...
+  const int c4 = tid & 63, w = tid >> 6;
+  float w3[4][MC], b3[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    b3[e] = prm[MP_B3 + 4 * c4 + e];
+#pragma unroll
+    for (int o = 0; o < MC; ++o) w3[e][o] = prm[MP_W3 + (4 * c4 + e) * MC + o];
+  }
+  for (int x = w; x < g; x += 4) {
+    const float* h = s_h + x * MC;
+    f32x4 d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a = b3[e];
+#pragma unroll
+      for (int o = 0; o < MC; ++o) a = fmaf(w3[e][o], h[o], a);
+      d[e] = a;
+    }
+    const int tok = y * g + x;
+    const f32x4 v = *(const f32x4*)(emb + ((int64_t)emb_rows[p] + tok) * ME + 4 * c4) + d;
+    const int64_t row = (int64_t)p * g * g + tok;
+    *(f32x4*)(keys + row * ME + 4 * c4) = v;
+    if (split) {
+      f16x4 hi, lo, hs;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        hi[e] = (f16)v[e];
+        lo[e] = (f16)((v[e] - (float)hi[e]) * 64.0f);
+        hs[e] = (f16)((float)hi[e] * 0.015625f);
+      }
+      f16* sp = split + row * 3 * ME + 4 * c4;
+      *(f16x4*)sp = hi;
+      *(f16x4*)(sp + ME) = lo;
+      *(f16x4*)(sp + 2 * ME) = hs;
+    }
+  }
 }
 
 // masks[n, 4y+2dy1+dy2, 4x+2dx1+dx2] = hyper[n,:] . up[((n*g*g + y*g + x)*4 + s1)*4 + s2, :]
@@ -197,5 +373,29 @@ extern "C" int ink_sam_postprocess(const float* low, int32_t n, int32_t S, int32
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipLaunchKernelGGL(postprocess_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, low, n, S,
                      L, in_h, in_w, out_h, out_w, thr, (uint8_t*)out_u8, out_logits);
+  return ink_launch_status();
+}
+
+extern "C" int ink_sam_prompt_tokens(const float* points, const int32_t* labels, int32_t n_pts, int32_t pad,
+                                     const float* boxes, const float* gauss, int32_t F, const float* point_emb,
+                                     const float* not_a_point, const float* out_tok, float input_size, int32_t P,
+                                     float* out, void* stream) {
+  INK_CHECK_ARG(gauss && point_emb && not_a_point && out_tok && out && P > 0 && F > 0 && input_size > 0.f);
+  INK_CHECK_ARG(n_pts >= 0 && (n_pts == 0 || (points && labels)) && (pad == 0 || pad == 1));
+  const int NT = 5 + n_pts + pad + (boxes ? 2 : 0);
+  INK_CHECK_ARG(NT <= 16);
+  const int64_t total = (int64_t)P * NT * F;
+  hipLaunchKernelGGL(prompt_tokens_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     points, labels, n_pts, pad, boxes, gauss, F, point_emb, not_a_point, out_tok, input_size, P, NT, out);
+  return ink_launch_status();
+}
+
+extern "C" int ink_sam_mask_embed(const float* mask, const float* emb, const int32_t* emb_rows, const float* params,
+                                  int32_t n_params, float eps, int32_t P, int32_t g, float* keys, void* split_f16,
+                                  void* stream) {
+  INK_CHECK_ARG(mask && emb && emb_rows && params && keys && P > 0 && g > 0 && g <= 64 && n_params == MP_TOTAL);
+  INK_CHECK_ARG((((uintptr_t)mask | (uintptr_t)emb | (uintptr_t)keys) & 15) == 0 && ((uintptr_t)split_f16 & 7) == 0);
+  hipLaunchKernelGGL(mask_embed_kernel, dim3((unsigned)(P * g)), dim3(256), 0, (hipStream_t)stream, mask, emb, emb_rows,
+                     params, eps, g, keys, (f16*)split_f16);
   return ink_launch_status();
 }

@@ -443,6 +443,58 @@ def sam_pe_encode(coords01: torch.Tensor, gauss: torch.Tensor,
     return out
 
 
+def sam_prompt_tokens(gauss: torch.Tensor, point_emb: torch.Tensor, not_a_point: torch.Tensor, out_tok: torch.Tensor,
+                      input_size: float, P: int, points: Optional[torch.Tensor] = None,
+                      labels: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, pad: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Token block of the SAM mask decoder for P prompts -> f32 [P, NT, 2F]: the 5 output tokens, the point tokens
+    (points f32 [P, N, 2], labels int32 [P, N], resized-input frame; pad appends (0, 0) with label -1), then the box
+    corners (boxes f32 [P, 4]).  NT = 5 + N + pad + 2 * (boxes given) <= 16.  See ink_sam_prompt_tokens."""
+    Fd = gauss.shape[1]
+    assert gauss.dtype == F32 and gauss.is_contiguous() and gauss.shape[0] == 2
+    for t, n in ((point_emb, 4), (not_a_point, 1), (out_tok, 5)):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == n * 2 * Fd
+    n_pts = 0
+    if points is not None:
+        assert labels is not None and points.dtype == F32 and labels.dtype == torch.int32
+        assert points.is_contiguous() and labels.is_contiguous() and points.dim() == 3 and points.shape[0] == P
+        n_pts = points.shape[1]
+        assert tuple(points.shape) == (P, n_pts, 2) and tuple(labels.shape) == (P, n_pts)
+    if boxes is not None:
+        assert boxes.dtype == F32 and boxes.is_contiguous() and tuple(boxes.shape) == (P, 4)
+    NT = 5 + n_pts + int(pad) + (2 if boxes is not None else 0)
+    if out is None:
+        out = torch.empty((P, NT, 2 * Fd), device=gauss.device, dtype=F32)
+    assert out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (P, NT, 2 * Fd)
+    check(_lib.lib().ink_sam_prompt_tokens(_p(points), _p(labels), n_pts, int(pad), _p(boxes), _p(gauss), Fd,
+                                           _p(point_emb), _p(not_a_point), _p(out_tok),
+                                           float(input_size), P, _p(out), _stream()), "ink_sam_prompt_tokens")
+    return out
+
+
+SAM_MASK_EMBED_PARAMS = 4684     # floats of the packed mask_downscaling parameters (see ink_sam_mask_embed)
+
+
+def sam_mask_embed(mask: torch.Tensor, emb: torch.Tensor, emb_rows: torch.Tensor, params: torch.Tensor, eps: float,
+                   split: bool = False):
+    """mask_input logits f32 [P, 1, 4g, 4g] -> the per-prompt keys emb[emb_rows[p] + t] + mask_downscaling(mask[p])[t],
+    f32 [P*g*g, 256] (and, with split=True, their split-f16 GEMM operand f16 [P*g*g, 768]; see add_split_f16).
+    emb f32 [*, 256] token rows; emb_rows int32 [P] (device) first row of each prompt's image."""
+    assert mask.dtype == F32 and mask.is_contiguous() and mask.dim() == 4 and mask.shape[1] == 1
+    P, S = mask.shape[0], mask.shape[2]
+    assert mask.shape[3] == S and S % 4 == 0
+    g = S // 4
+    assert emb.dtype == F32 and emb.is_contiguous() and emb.dim() == 2 and emb.shape[1] == 256
+    assert emb_rows.dtype == torch.int32 and emb_rows.is_cuda and emb_rows.numel() == P
+    assert params.dtype == F32 and params.is_contiguous() and params.numel() == SAM_MASK_EMBED_PARAMS
+    keys = torch.empty((P * g * g, 256), device=mask.device, dtype=F32)
+    ks = torch.empty((P * g * g, 768), device=mask.device, dtype=F16) if split else None
+    check(_lib.lib().ink_sam_mask_embed(_p(mask), _p(emb), _p(emb_rows), _p(params),
+                                        params.numel(), eps, P, g, _p(keys), _p(ks), _stream()),
+          "ink_sam_mask_embed")
+    return (keys, ks) if split else keys
+
+
 def sam_mask_logits(up: torch.Tensor, hyper: torch.Tensor, n: int, g: int) -> torch.Tensor:
     """hyper[n,C] . up[(((b*g*g + tok)*4 + s1)*4 + s2), C] -> pixel-shuffled [n, 4g, 4g] f32."""
     assert up.dtype == F32 and up.is_contiguous() and hyper.dtype == F32 and hyper.is_contiguous()
@@ -770,6 +822,25 @@ def sam_upscale_tail(u0: torch.Tensor, n: int, g: int, ln_g: torch.Tensor, ln_b:
     return low
 
 
+def sam_upscale_tail_masks(u0: torch.Tensor, n: int, g: int, ln_g: torch.Tensor, ln_b: torch.Tensor, eps: float,
+                           blob: torch.Tensor, b3: torch.Tensor, hyper: torch.Tensor) -> torch.Tensor:
+    """sam_upscale_tail for M in {1, 3, 4} mask tokens per box at once: hyper f32 [n, M, 32] -> low-res logits f32
+    [n, M, 4g, 4g].  The upscaling is computed once per row and shared by the M masks."""
+    if u0.shape[1] == 64:
+        assert u0.is_contiguous() and u0.shape[0] == n * g * g * 4
+        u0 = u0.view(n * g * g, 256)
+    assert u0.dtype == F32 and u0.stride(1) == 1 and tuple(u0.shape) == (n * g * g, 256) and u0.stride(0) % 4 == 0
+    assert blob.dtype == F16 and blob.numel() == 4 * 12 * 64 * 8 and b3.dtype == F32 and b3.numel() == 128
+    assert hyper.dtype == F32 and hyper.is_contiguous() and hyper.dim() == 3 and hyper.shape[0] == n and hyper.shape[2] == 32
+    assert ln_g.dtype == F32 and ln_b.dtype == F32 and ln_g.numel() == 64 and ln_b.numel() == 64
+    M = hyper.shape[1]
+    low = torch.empty((n, M, 4 * g, 4 * g), device=u0.device, dtype=F32)
+    check(_lib.lib().ink_sam_upscale_tail_masks(_p(u0), u0.stride(0), n, g, _p(ln_g), _p(ln_b), eps,
+                                                _p(blob), _p(b3), _p(hyper), M, _p(low),
+                                                _stream()), "ink_sam_upscale_tail_masks")
+    return low
+
+
 def ffn256_pack(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, w_pre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """linear1.weight f16 [hid, 256] + linear1.bias f32 [hid] + linear2.weight f16 [256, hid] (+ the weight f16 [256, 256] of
     a preceding projection, see ffn256_fused) -> the packed weight blob (done once at load time; csrc/ffn_fused.hip)."""
@@ -840,7 +911,8 @@ def attn_fewkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n
 def attn_fewq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: int, n_heads: int, head_dim: int,
               scale: float, n_q: int, n_k: int, q_batch_rows: Optional[torch.Tensor] = None,
               kv_batch_rows: Optional[torch.Tensor] = None, k_add: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Few queries (<= 8) against many keys; same row conventions as flash_attn.  q/k/v/out all f16 or all f32."""
+    """Few queries (<= 8; <= 16 with f32 rows) against many keys; same row conventions as flash_attn.  q/k/v/out all
+    f16 or all f32."""
     io = q.dtype
     for t in (q, k, v):
         assert t.dtype == io and io in (F16, F32) and t.dim() == 2 and t.stride(1) == 1

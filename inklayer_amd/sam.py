@@ -77,6 +77,97 @@ def resize_longest_side(img: np.ndarray, L: int) -> np.ndarray:
     return np.asarray(Image.fromarray(img).resize((nw, nh), Image.BILINEAR))
 
 
+MAX_TOKENS = 16      # decoder tokens per prompt: 5 output tokens + points (+ pad) + box corners (ink_attn_fewq / _fewkeys)
+
+
+def _hyp(m: int) -> str:
+    """Weight-key prefix of mask token m's hyper-network MLP ('hyp' for token 0, as before multimask output)."""
+    return "hyp" if m == 0 else f"m{m}hyp"
+
+
+def check_prompts(point_coords=None, point_labels=None, boxes=None, mask_input=None,
+                  mask_side: int = 256) -> Tuple[int, int]:
+    """Validate the batched prompts of SamPredictor.predict_torch (SA/predictor.py:160-243) before anything is launched:
+    point_coords [P, N, 2] float with point_labels [P, N] (integer values), boxes [P, 4] float, mask_input
+    [P, 1, mask_side, mask_side] float; every given prompt has the same P.  Points without a box get one padding point
+    (prompt_encoder.py:150-151).  Returns (P, NT), NT = 5 output tokens + sparse tokens; raises ValueError for a bad
+    shape or dtype and for NT > MAX_TOKENS (10 points alone, or a box plus 9 points).  Pure host code."""
+    def shape(t):
+        return tuple(t.shape) if hasattr(t, "shape") else None
+
+    def is_float(t):
+        return (t.dtype.is_floating_point if isinstance(t.dtype, torch.dtype)
+                else np.issubdtype(np.dtype(t.dtype), np.floating))
+
+    def is_int_valued(t):
+        if isinstance(t.dtype, torch.dtype):
+            return not t.dtype.is_complex and t.dtype != torch.bool and (
+                not t.dtype.is_floating_point or bool(torch.all(t == torch.round(t))))
+        d = np.dtype(t.dtype)
+        return np.issubdtype(d, np.integer) or (np.issubdtype(d, np.floating) and bool(np.all(t == np.round(t))))
+
+    Ps = []
+    n_sparse = 0
+    if (point_coords is None) != (point_labels is None):
+        raise ValueError("point_coords and point_labels must be given together")
+    if point_coords is not None:
+        sc, sl = shape(point_coords), shape(point_labels)
+        if sc is None or len(sc) != 3 or sc[2] != 2 or not is_float(point_coords):
+            raise ValueError(f"point_coords must be a float tensor [P, N, 2], got {sc}")
+        if sl != sc[:2] or not is_int_valued(point_labels):
+            raise ValueError(f"point_labels must be integer labels [P, N] = {list(sc[:2])}, got {sl}")
+        Ps.append(sc[0])
+        n_sparse += sc[1] + (1 if boxes is None else 0)
+    if boxes is not None:
+        sb = shape(boxes)
+        if sb is None or len(sb) != 2 or sb[1] != 4 or not is_float(boxes):
+            raise ValueError(f"boxes must be a float tensor [P, 4], got {sb}")
+        Ps.append(sb[0])
+        n_sparse += 2
+    if mask_input is not None:
+        sm = shape(mask_input)
+        if sm is None or len(sm) != 4 or sm[1:] != (1, mask_side, mask_side) or not is_float(mask_input):
+            raise ValueError(f"mask_input must be float low-res logits [P, 1, {mask_side}, {mask_side}], got {sm}")
+        Ps.append(sm[0])
+    P = Ps[0] if Ps else 1
+    if any(p != P for p in Ps):
+        raise ValueError(f"the prompts disagree on the batch size: {Ps}")
+    if P < 1:
+        raise ValueError("at least one prompt is needed")
+    NT = 5 + n_sparse
+    if NT > MAX_TOKENS:
+        raise ValueError(f"{NT} decoder tokens per prompt (5 + {n_sparse} sparse) exceed the limit of {MAX_TOKENS}: "
+                         f"at most 10 points without a box, or a box plus 9 points")
+    return P, NT
+
+
+class ResizeLongestSide:
+    """Coordinate half of SA/utils/transforms.py:16-102 (the image half is ops.resize_bilinear_u8)."""
+
+    def __init__(self, target_length: int):
+        self.target_length = target_length
+
+    def apply_coords(self, coords: np.ndarray, original_size: Tuple[int, int]) -> np.ndarray:
+        (oh, ow), (nh, nw) = original_size, preprocess_shape(original_size[0], original_size[1], self.target_length)
+        c = np.array(coords, dtype=float)          # copy, float64 as the reference's astype(float)
+        c[..., 0] = c[..., 0] * (nw / ow)
+        c[..., 1] = c[..., 1] * (nh / oh)
+        return c
+
+    def apply_boxes(self, boxes: np.ndarray, original_size: Tuple[int, int]) -> np.ndarray:
+        return self.apply_coords(np.asarray(boxes).reshape(-1, 2, 2), original_size).reshape(-1, 4)
+
+    def apply_coords_torch(self, coords: torch.Tensor, original_size: Tuple[int, int]) -> torch.Tensor:
+        (oh, ow), (nh, nw) = original_size, preprocess_shape(original_size[0], original_size[1], self.target_length)
+        c = coords.detach().clone().to(torch.float)
+        c[..., 0] = c[..., 0] * (nw / ow)
+        c[..., 1] = c[..., 1] * (nh / oh)
+        return c
+
+    def apply_boxes_torch(self, boxes: torch.Tensor, original_size: Tuple[int, int]) -> torch.Tensor:
+        return self.apply_coords_torch(boxes.reshape(-1, 2, 2), original_size).reshape(-1, 4)
+
+
 def _to_dev_async(t: torch.Tensor, dev) -> torch.Tensor:
     """Small host tensor -> device through pinned memory, non-blocking.  A pageable `.to(dev)` makes the host wait
     until the stream has drained (here: the whole image encoder) before it can queue the decoder's launches."""
@@ -165,6 +256,19 @@ class SamEngine:
         w["corner"] = torch.cat([f("prompt_encoder.point_embeddings.2.weight"),
                                  f("prompt_encoder.point_embeddings.3.weight")], 0).contiguous()
         w["no_mask"] = f("prompt_encoder.no_mask_embed.weight").reshape(-1).contiguous()
+        # point and mask prompts (SamEngine.decode_prompts).  A state dict made for the box path alone may lack these
+        # weights: they are then absent here and decode_prompts names what is missing.
+        # point_embeddings 0..3 (negative, positive, box corners) and not_a_point_embed
+        w["pt_emb"] = torch.cat([f(f"prompt_encoder.point_embeddings.{i}.weight") for i in range(4)], 0).contiguous()
+        if "prompt_encoder.not_a_point_embed.weight" in sd:
+            w["not_a_point"] = f("prompt_encoder.not_a_point_embed.weight").reshape(-1).contiguous()
+        # mask_downscaling's ten tensors flattened into one f32 block (layout: ink_sam_mask_embed)
+        md = "prompt_encoder.mask_downscaling."
+        md_names = ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight", "3.bias", "4.weight", "4.bias", "6.weight",
+                    "6.bias")
+        if all(md + n in sd for n in md_names):
+            w["mask_ds"] = torch.cat([sd[md + n].detach().to(torch.float32).reshape(-1) for n in md_names]) \
+                .to(dev).contiguous()
         # dense positional encoding of the 64x64 grid (prompt_encoder.py:195-206): constant
         ar = (torch.arange(g, dtype=torch.float32) + 0.5) / g
         grid_xy = torch.stack([ar[None, :].expand(g, g), ar[:, None].expand(g, g)], -1).reshape(-1, 2)
@@ -209,6 +313,9 @@ class SamEngine:
             w[f"hyp{j}.b"] = f(f"mask_decoder.output_hypernetworks_mlps.0.layers.{j}.bias")
             w[f"iou{j}.w"] = h(f"mask_decoder.iou_prediction_head.layers.{j}.weight")
             w[f"iou{j}.b"] = f(f"mask_decoder.iou_prediction_head.layers.{j}.bias")
+            for m in range(1, cfg.num_mask_tokens):   # mask tokens 1..3 (multimask output; split-f16 path only)
+                if f"mask_decoder.output_hypernetworks_mlps.{m}.layers.{j}.bias" in sd:
+                    w[f"{_hyp(m)}{j}.b"] = f(f"mask_decoder.output_hypernetworks_mlps.{m}.layers.{j}.bias")
         # the last hyper layer has N = 32 outputs, the iou head N = 4: both fine for the GEMM (N % 4)
 
         if self.precise_tail:
@@ -310,6 +417,10 @@ class SamEngine:
         for j in range(3):
             w[f"hyp{j}.ws"] = ops.split_weight(m(f"mask_decoder.output_hypernetworks_mlps.0.layers.{j}.weight"))
             w[f"iou{j}.ws"] = ops.split_weight(m(f"mask_decoder.iou_prediction_head.layers.{j}.weight"))
+            for k in range(1, cfg.num_mask_tokens):
+                if f"mask_decoder.output_hypernetworks_mlps.{k}.layers.{j}.weight" in sd:
+                    w[f"{_hyp(k)}{j}.ws"] = ops.split_weight(
+                        m(f"mask_decoder.output_hypernetworks_mlps.{k}.layers.{j}.weight"))
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int) -> None:
@@ -632,32 +743,93 @@ class SamEngine:
         return low, iou
 
     def _decode_low_res_split(self, emb: torch.Tensor, boxes: torch.Tensor, img_of_box: Sequence[int]):
-        """decode_low_res on split-f16 operands: every activation stays f32, every projection multiplies a
-        [hi | lo*64 | hi/64] operand (ops.add_split_f16 / layernorm_rows(split=True)) with a '.ws' weight, the three
-        attentions read and write f32 rows.  Same structure as the reference (mask_decoder.py:112-149,
-        transformer.py:62-106,151-182)."""
-        cfg, w, T, dev = self.cfg, self.w, self.T, self.dev
-        E, L, g = cfg.prompt_embed_dim, cfg.img_size, cfg.grid
-        B = emb.shape[0]
+        """decode_low_res on split-f16 operands (box prompts, mask token 0): the token block, then
+        _decode_tokens_split."""
+        cfg, w, dev = self.cfg, self.w, self.dev
+        E, L = cfg.prompt_embed_dim, cfg.img_size
         n = boxes.shape[0]
         assert n > 0 and len(img_of_box) == n
-        NT, Hh = 5 + 2, cfg.dec_heads
-        SP = ops.add_split_f16
-
-        def lin(x_split, name, bias=True, **kw):
-            return ops.gemm(x_split, w[name + ".ws"], w[name + ".b"] if bias else None, **kw)
-
+        NT = 5 + 2
         coords = _to_dev_async((boxes + 0.5).reshape(-1, 2) / float(L), dev)
         sparse = ops.sam_pe_encode(coords, w["gauss"], add=w["corner"])           # [2n, E]
         tokens = torch.empty((n, NT, E), device=dev, dtype=F32)
         tokens[:, :5] = w["out_tok"]
         tokens[:, 5:] = sparse.view(n, 2, E)
+        low, iou = self._decode_tokens_split(emb, tokens, img_of_box)
+        return low.view(n, *low.shape[-2:]), iou
+
+    def decode_prompts(self, emb: torch.Tensor, img_of_prompt: Sequence[int], points: Optional[torch.Tensor] = None,
+                       labels: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None,
+                       mask_input: Optional[torch.Tensor] = None, multimask_output: bool = False,
+                       masks: Optional[Tuple[int, int]] = None):
+        """Prompt encoder + mask decoder for P prompts of any form (SA/modeling/prompt_encoder.py:128-166,
+        mask_decoder.py:71-149), spread over the B images of emb [B, 4096, 256] f32 (img_of_prompt[p] = image of prompt p).
+        points f32 [P, N, 2] + labels int [P, N], boxes f32 [P, 4] (both in the resized-input frame), mask_input f32
+        [P, 1, 256, 256] low-res logits; any of them may be None (check_prompts states the rules).  The token block
+        comes from one kernel (ops.sam_prompt_tokens); a mask input makes the keys per prompt from layer 0 on
+        (ops.sam_mask_embed).  multimask_output selects mask tokens 1..3, else token 0; masks = (first, count) overrides
+        it (count in {1, 3, 4}).  -> (low-res logits [P, M, 256, 256] f32, iou [P, M] f32)."""
+        if not self.precise_tail:
+            raise NotImplementedError("point / mask prompts and multimask output run on the split-f16 decoder only "
+                                      "(SamEngine(precise_tail=True), the product setting)")
+        cfg, w, dev, L = self.cfg, self.w, self.dev, self.cfg.img_size
+        P, _ = check_prompts(points, labels, boxes, mask_input, mask_side=4 * cfg.grid)
+        if len(img_of_prompt) != P or not all(0 <= int(i) < emb.shape[0] for i in img_of_prompt):
+            raise ValueError(f"img_of_prompt must name an image of emb for each of the {P} prompts")
+        lo, M = masks if masks is not None else ((1, 3) if multimask_output else (0, 1))
+        if M not in (1, 3, 4) or not 0 <= lo <= cfg.num_mask_tokens - M:
+            raise ValueError(f"masks=(first, count) must select 1, 3 or 4 of the {cfg.num_mask_tokens} mask tokens")
+        need = [("not_a_point", points is not None, "prompt_encoder.not_a_point_embed"),
+                ("mask_ds", mask_input is not None, "prompt_encoder.mask_downscaling")]
+        need += [(f"{_hyp(m)}0.ws", m > 0, f"mask_decoder.output_hypernetworks_mlps.{m}") for m in range(lo, lo + M)]
+        missing = [name for key, used, name in need if used and key not in w]
+        if missing:
+            raise ValueError(f"these prompts need weights the engine's state dict did not have: {missing}")
+
+        def dev32(t, dt=F32):
+            t = torch.as_tensor(t)
+            return t.to(dev, dt).contiguous() if t.is_cuda else _to_dev_async(t.to(dt), dev)
+
+        pts = lab = bx = None
+        if points is not None:
+            pts, lab = dev32(points), dev32(labels, torch.int32)
+        if boxes is not None:
+            bx = dev32(torch.as_tensor(boxes).reshape(-1, 4))
+        tokens = ops.sam_prompt_tokens(w["gauss"], w["pt_emb"], w["not_a_point"], w["out_tok"], float(L), P, points=pts,
+                                       labels=lab, boxes=bx, pad=points is not None and boxes is None)
+        mi = dev32(mask_input) if mask_input is not None else None
+        return self._decode_tokens_split(emb, tokens, img_of_prompt, mask_input=mi, mask_lo=lo, n_masks=M)
+
+    def _decode_tokens_split(self, emb: torch.Tensor, tokens: torch.Tensor, img_of_box: Sequence[int],
+                             mask_input: Optional[torch.Tensor] = None, mask_lo: int = 0, n_masks: int = 1):
+        """The mask decoder on split-f16 operands: every activation stays f32, every projection multiplies a
+        [hi | lo*64 | hi/64] operand (ops.add_split_f16 / layernorm_rows(split=True)) with a '.ws' weight, the three
+        attentions read and write f32 rows.  Same structure as the reference (mask_decoder.py:112-149,
+        transformer.py:62-106,151-182).  tokens f32 [n, NT, E] (NT <= 16); mask_input f32 [n, 1, 4g, 4g] or None;
+        mask tokens mask_lo .. mask_lo + n_masks - 1.  -> (low [n, n_masks, 4g, 4g], iou [n, n_masks])."""
+        cfg, w, T, dev = self.cfg, self.w, self.T, self.dev
+        E, g = cfg.prompt_embed_dim, cfg.grid
+        B = emb.shape[0]
+        n, NT = tokens.shape[0], tokens.shape[1]
+        assert n > 0 and len(img_of_box) == n and NT <= MAX_TOKENS
+        Hh = cfg.dec_heads
+        SP = ops.add_split_f16
+
+        def lin(x_split, name, bias=True, **kw):
+            return ops.gemm(x_split, w[name + ".ws"], w[name + ".b"] if bias else None, **kw)
+
         qpe = tokens.view(n * NT, E)
         iob = torch.as_tensor(list(img_of_box), dtype=torch.int64)
         img_rows = _to_dev_async((iob * T).to(torch.int32), dev)
-        keys = ops.add_f32(emb.reshape(B * T, E).contiguous(), w["no_mask"])      # [B*T, E], shared per image
-        shared = True                                       # keys still one copy per IMAGE (layer 0)
-        ks = None                                           # split-f16 operand of the per-box keys (layers >= 1)
+        if mask_input is None:
+            keys = ops.add_f32(emb.reshape(B * T, E).contiguous(), w["no_mask"])      # [B*T, E], shared per image
+            shared = True                                   # keys still one copy per IMAGE (layer 0)
+            ks = None                                       # split-f16 operand of the per-box keys (layers >= 1)
+        else:
+            # src = emb + mask_downscaling(mask) (mask_decoder.py:123-126): per-prompt keys and their split operand
+            keys, ks = ops.sam_mask_embed(mask_input, emb.reshape(B * T, E).contiguous(), img_rows, w["mask_ds"], 1e-6,
+                                          split=True)
+            shared = False
         queries = qpe
         sc32, sc16 = 1.0 / math.sqrt(32), 1.0 / math.sqrt(16)
 
@@ -733,31 +905,43 @@ class SamEngine:
             a = lin(SP(a), prefix + "1", act="relu")
             return lin(SP(a), prefix + "2")
 
-        hyper = mlp3("hyp", hs[:, 1].contiguous())          # mask token 0 -> [n, 32]
-        iou = mlp3("iou", hs[:, 0].contiguous())[:, :1]     # iou token -> [n, 4] -> mask 0
+        M = n_masks
+        if mask_lo == 0 and M == 1:
+            hyper = mlp3("hyp", hs[:, 1].contiguous())      # mask token 0 -> [n, 32]
+        else:                                               # tokens mask_lo .. mask_lo + M - 1 -> [n, M, 32]
+            hyper = torch.stack([mlp3(_hyp(m), hs[:, 1 + m].contiguous()) for m in range(mask_lo, mask_lo + M)], 1)
+        iou = mlp3("iou", hs[:, 0].contiguous())[:, mask_lo:mask_lo + M]     # iou token -> [n, 4] -> the M masks
         u0 = kvu[:, 2 * Eh:]                                                     # [n*T, 4*64], row stride 512
         if "up3.blob" in w and (T * 4) % 32 == 0:
             # LayerNorm2d + GELU + the second transposed convolution + GELU + the hyper-network product in one kernel
-            # (csrc/upscale_tail.hip): u0 is read once, 4 floats per row are written
-            low = ops.sam_upscale_tail(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"],
-                                       hyper.contiguous())
+            # (csrc/upscale_tail.hip): u0 is read once, 4 floats per row and mask are written
+            if M == 1:
+                low = ops.sam_upscale_tail(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"],
+                                           hyper.reshape(n, 32).contiguous())
+            else:
+                low = ops.sam_upscale_tail_masks(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"], hyper)
         else:
             u1 = ops.layernorm_rows(u0.contiguous().view(n * T * 4, E // 4), w["up1.w"], w["up1.b"], 1e-6, act="gelu",
                                     split=True)
             u2 = lin(u1, "up3", act="gelu")                                          # [n*T*4, 4*32]
-            low = ops.sam_mask_logits(u2, hyper.contiguous(), n, g)                   # [n, 256, 256]
-        return low, iou
+            hyp3 = hyper.reshape(n, M, 32)
+            low = torch.stack([ops.sam_mask_logits(u2, hyp3[:, m].contiguous(), n, g) for m in range(M)], 1) \
+                if M > 1 else ops.sam_mask_logits(u2, hyp3[:, 0].contiguous(), n, g)  # [n, (M,) 256, 256]
+        return low.view(n, M, 4 * g, 4 * g), iou
 
 
 # ----------------------------------------------------------------------------------------
 # reference-shaped API
 # ----------------------------------------------------------------------------------------
 class SamPredictor:
-    """Same call surface as SA/predictor.py:17-243 for the box-prompt path InkLayer uses."""
+    """Same call surface as SA/predictor.py:17-243: point, box and mask prompts, single or multimask output.
+    One divergence: predict_torch defaults to multimask_output=False (InkLayer's box call); predict keeps the
+    reference's True."""
 
     def __init__(self, engine: SamEngine):
         self.engine = engine
         self.cfg = engine.cfg
+        self.transform = ResizeLongestSide(engine.cfg.img_size)
         self.reset_image()
 
     def reset_image(self) -> None:
@@ -788,17 +972,58 @@ class SamPredictor:
         c[..., 1] = c[..., 1] * (nh / oh)
         return c.reshape(-1, 4)
 
-    def predict_torch(self, point_coords=None, point_labels=None, boxes: torch.Tensor = None,
-                      mask_input=None, multimask_output: bool = False, return_logits: bool = False):
+    def apply_coords(self, coords: np.ndarray, original_size: Optional[Tuple[int, int]] = None) -> np.ndarray:
+        """ResizeLongestSide.apply_coords (SA/utils/transforms.py:33-45): original-image pixels -> input frame."""
+        return self.transform.apply_coords(coords, original_size or self.original_size)
+
+    def apply_coords_torch(self, coords: torch.Tensor, original_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        """ResizeLongestSide.apply_coords_torch (SA/utils/transforms.py:67-81)."""
+        return self.transform.apply_coords_torch(coords, original_size or self.original_size)
+
+    def predict(self, point_coords: Optional[np.ndarray] = None, point_labels: Optional[np.ndarray] = None,
+                box: Optional[np.ndarray] = None, mask_input: Optional[np.ndarray] = None,
+                multimask_output: bool = True, return_logits: bool = False):
+        """SA/predictor.py:92-158: one prompt in original-image pixels (point_coords [N, 2], point_labels [N], box [4],
+        mask_input [1, 256, 256] low-res logits) -> numpy (masks [C, H, W], iou [C], low-res logits [C, 256, 256])."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        if point_coords is not None or mask_input is not None or multimask_output:
-            raise NotImplementedError("InkLayer only uses box prompts with multimask_output=False")
-        masks, low, iou, logits = self.engine.decode(self.features, boxes.detach().cpu(), self.input_size,
-                                                     self.original_size, want_logits=True)
-        n = masks.shape[0]
-        out = logits if return_logits else masks.bool()
-        return out.view(n, 1, *self.original_size), iou, low.view(n, 1, *low.shape[-2:])
+        if point_coords is not None and point_labels is None:
+            raise ValueError("point_labels must be supplied if point_coords is supplied.")
+        coords = labels = boxes = mask = None
+        if point_coords is not None:
+            coords = torch.as_tensor(self.apply_coords(point_coords), dtype=torch.float)[None]
+            labels = torch.as_tensor(np.asarray(point_labels), dtype=torch.int)[None]
+        if box is not None:
+            boxes = torch.as_tensor(self.transform.apply_boxes(box, self.original_size), dtype=torch.float)[:1]
+        if mask_input is not None:
+            mask = torch.as_tensor(mask_input, dtype=torch.float)[None]
+        masks, iou, low = self.predict_torch(coords, labels, boxes, mask, multimask_output, return_logits=return_logits)
+        return masks[0].cpu().numpy(), iou[0].cpu().numpy(), low[0].cpu().numpy()
+
+    def predict_torch(self, point_coords=None, point_labels=None, boxes: torch.Tensor = None,
+                      mask_input=None, multimask_output: bool = False, return_logits: bool = False):
+        """SA/predictor.py:160-243 with batched prompts already in the input frame: point_coords [B, N, 2],
+        point_labels [B, N], boxes [B, 4], mask_input [B, 1, 256, 256].  -> (masks [B, C, H, W] bool (f32 logits with
+        return_logits), iou [B, C], low-res logits [B, C, 256, 256]); C = 3 with multimask_output, else 1."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if point_coords is None and point_labels is None and mask_input is None and not multimask_output \
+                and boxes is not None:
+            # box prompts, mask token 0: InkLayer's call (decode_low_res)
+            masks, low, iou, logits = self.engine.decode(self.features, boxes.detach().cpu(), self.input_size,
+                                                         self.original_size, want_logits=True)
+            n = masks.shape[0]
+            out = logits if return_logits else masks.bool()
+            return out.view(n, 1, *self.original_size), iou, low.view(n, 1, *low.shape[-2:])
+        eng = self.engine
+        P, _ = check_prompts(point_coords, point_labels, boxes, mask_input, mask_side=4 * self.cfg.grid)
+        low, iou = eng.decode_prompts(self.features.reshape(1, eng.T, -1), [0] * P, point_coords, point_labels, boxes,
+                                      mask_input, multimask_output)
+        C, S = low.shape[1], low.shape[-1]
+        res = ops.sam_postprocess(low.view(P * C, S, S), self.cfg.img_size, self.input_size, self.original_size,
+                                  self.cfg.mask_threshold, return_logits)
+        out = res[1] if return_logits else res.bool()
+        return out.view(P, C, *self.original_size), iou, low
 
 
 _ENGINES: Dict[str, SamEngine] = {}
