@@ -205,6 +205,20 @@ class _Plan:
         self.valid_map = torch.where(valid, torch.arange(self.S), torch.full((self.S,), -1)).to(I32).to(dev)
 
 
+def swin_dense_bias(table: torch.Tensor, ws: int, nh: int, scale: float) -> torch.Tensor:
+    """The relative-position bias of one Swin block (swin_transformer.py:111-121, 159-163) as flash_attn's dense_bias:
+    f32 [nh, ws*ws, 64], query rows x key columns, pre-divided by the softmax scale, columns ws*ws.. zero."""
+    co = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
+    rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0).contiguous()
+    rel[:, :, 0] += ws - 1
+    rel[:, :, 1] += ws - 1
+    rel[:, :, 0] *= 2 * ws - 1
+    rel_index = rel.sum(-1).view(-1)
+    bias = torch.zeros((nh, ws * ws, 64))
+    bias[:, :, :ws * ws] = table[rel_index].view(ws * ws, ws * ws, nh).permute(2, 0, 1) / scale
+    return bias
+
+
 def clean_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """clean_state_dict (GD/util/misc.py:711-717): strip the DataParallel "module." prefix the shipped
     GroundingDINO checkpoints carry (GD/util/inference.py:33-34 always applies it)."""
@@ -254,12 +268,6 @@ class GDinoEngine:
         w["pe.b"] = f(bb + "patch_embed.proj.bias")
         ln("pe.norm", bb + "patch_embed.norm")
         ws = cfg.window_size
-        co = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
-        rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0).contiguous()
-        rel[:, :, 0] += ws - 1
-        rel[:, :, 1] += ws - 1
-        rel[:, :, 0] *= 2 * ws - 1
-        rel_index = rel.sum(-1).view(-1)
         scale = 32 ** -0.5
         for i, (dep, nh) in enumerate(zip(cfg.depths, cfg.num_heads)):
             for b in range(dep):
@@ -271,9 +279,7 @@ class GDinoEngine:
                 lin(d + ".fc1", p + "mlp.fc1")
                 lin(d + ".fc2", p + "mlp.fc2")
                 tab = sd[p + "attn.relative_position_bias_table"].detach().to(torch.float32).cpu()
-                bias = torch.zeros((nh, ws * ws, 64))
-                bias[:, :, :ws * ws] = tab[rel_index].view(ws * ws, ws * ws, nh).permute(2, 0, 1) / scale
-                w[d + ".bias"] = bias.to(dev).contiguous()
+                w[d + ".bias"] = swin_dense_bias(tab, ws, nh, scale).to(dev).contiguous()
             if i < len(cfg.depths) - 1:
                 ln(f"s{i}.merge.norm", f"{bb}layers.{i}.downsample.norm")
                 w[f"s{i}.merge.w"] = h(f"{bb}layers.{i}.downsample.reduction.weight")
@@ -419,6 +425,24 @@ class GDinoEngine:
         a = ops.gemm(a, w[prefix + "1.w"], w[prefix + "1.b"], act="relu", out_dtype=F16)
         return ops.gemm(a, w[prefix + "2.w"], w[prefix + "2.b"])
 
+    def _swin_block(self, x: torch.Tensor, i: int, b: int, pl: _Plan) -> None:
+        """Block b of Swin stage i (SwinTransformerBlock.forward, swin_transformer.py:238-298) on the f32 tokens
+        x [B*H*W, C] of that stage, in place."""
+        cfg, w = self.cfg, self.w
+        C, nh, nW = cfg.embed_dim * 2 ** i, cfg.num_heads[i], pl.nW[i]
+        d = f"s{i}b{b}"
+        shifted = b % 2 == 1
+        wm = pl.win_map[i][1 if shifted else 0]
+        y = ops.layernorm_rows(x, w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, gather=wm)
+        qkv = ops.gemm(y, w[d + ".qkv.w"], w[d + ".qkv.b"], out_dtype=F16)
+        o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_batch=pl.B * nW, n_heads=nh,
+                           head_dim=32, scale=32 ** -0.5, n_q=49, n_k=49, dense_bias=w[d + ".bias"],
+                           dense_mask=pl.shift_mask[i] if shifted else None)
+        ops.gemm(o, w[d + ".proj.w"], w[d + ".proj.b"], residual=x, row_map=wm, out=x)
+        y = ops.layernorm_rows(x, w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5)
+        hmid = ops.gemm(y, w[d + ".fc1.w"], w[d + ".fc1.b"], act="gelu", out_dtype=F16)
+        ops.gemm(hmid, w[d + ".fc2.w"], w[d + ".fc2.b"], residual=x, out=x)
+
     def backbone(self, images_u8: Sequence[torch.Tensor], pl: _Plan) -> Dict[int, Tuple[torch.Tensor, torch.Tensor]]:
         """Swin-T (swin_transformer.py:712-754): {stage: (f32 tokens, f16 tokens)} after norm{i}."""
         cfg, w, dev = self.cfg, self.w, self.dev
@@ -431,23 +455,9 @@ class GDinoEngine:
         x = ops.gemm(patches, w["pe.w"], w["pe.b"])
         x = ops.layernorm_rows(x, w["pe.norm.w"], w["pe.norm.b"], 1e-5, out_dtype=F32)
         outs = {}
-        scale = 32 ** -0.5
-        for i, (dep, nh) in enumerate(zip(cfg.depths, cfg.num_heads)):
-            C = cfg.embed_dim * 2 ** i
-            nW = pl.nW[i]
+        for i, dep in enumerate(cfg.depths):
             for b in range(dep):
-                d = f"s{i}b{b}"
-                shifted = b % 2 == 1
-                wm = pl.win_map[i][1 if shifted else 0]
-                y = ops.layernorm_rows(x, w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, gather=wm)
-                qkv = ops.gemm(y, w[d + ".qkv.w"], w[d + ".qkv.b"], out_dtype=F16)
-                o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_batch=B * nW, n_heads=nh,
-                                   head_dim=32, scale=scale, n_q=49, n_k=49, dense_bias=w[d + ".bias"],
-                                   dense_mask=pl.shift_mask[i] if shifted else None)
-                ops.gemm(o, w[d + ".proj.w"], w[d + ".proj.b"], residual=x, row_map=wm, out=x)
-                y = ops.layernorm_rows(x, w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5)
-                hmid = ops.gemm(y, w[d + ".fc1.w"], w[d + ".fc1.b"], act="gelu", out_dtype=F16)
-                ops.gemm(hmid, w[d + ".fc2.w"], w[d + ".fc2.b"], residual=x, out=x)
+                self._swin_block(x, i, b, pl)
             if i in cfg.out_indices:
                 o32 = torch.empty_like(x)
                 o16 = torch.empty(x.shape, device=dev, dtype=F16)

@@ -88,18 +88,6 @@ def test_config3_batch8_x16_boxes_against_oracle(dev, bench_pipeline):
     print(f"config 3: {len(all_iou)} instances, IoU min {min(all_iou):.5f} median {np.median(all_iou):.5f}")
 
     # ---------------- detector at the bench's size (800x800 -> 13294 tokens, 6+6 layers, 900 queries)
-    import torch.nn.functional as RealF
-
-    class _F16Operands:
-        def __getattr__(self, k):
-            return getattr(RealF, k)
-
-        def linear(self, a, w, b=None):
-            return RealF.linear(a.half().float(), w.half().float(), b)
-
-        def conv2d(self, a, w, b=None, **kw):
-            return RealF.conv2d(a.half().float(), w.half().float(), b, **kw)
-
     det = pipe.det
     det_in, _, _ = pipe.preprocess(pipe.upload(imgs))
     st = {}
@@ -127,11 +115,8 @@ def test_config3_batch8_x16_boxes_against_oracle(dev, bench_pipeline):
             assert l2 < 5e-3
         d = (both[b, :, T:] - ref_boxes[0]).abs().max(-1)[0]
         dl = (both[b, :, :T] - ref_logits[0]).abs().max(-1)[0] / ref_logits.abs().max()
-        gdino_ref.F = _F16Operands()
-        try:
+        with gdino_ref.f16_operands():
             el, eb = gdino_ref.detector_forward(gsd, ocfg, x[None], text, sm, pid, stages=dict(pin))
-        finally:
-            gdino_ref.F = RealF
         sb = (eb[0] - ref_boxes[0]).abs().max(-1)[0]
         sl = (el[0] - ref_logits[0]).abs().max(-1)[0] / ref_logits.abs().max()
         for name, mine, emul in (("box", d, sb), ("logit", dl, sl)):

@@ -1,5 +1,6 @@
 """HIP GroundingDINO path vs the CPU oracle (oracle/gdino_ref.py, pinned to the reference by
 tests/golden/gdino_small.npz).  GPU box only."""
+import contextlib
 from pathlib import Path
 
 import numpy as np
@@ -179,31 +180,16 @@ def test_detector_stages_match_oracle(dev, small_dino):
     #   (1) every quantile of the HIP error INCLUDING THE MAXIMUM is bounded by 2x the emulated-f16 oracle's, and
     #   (2) per query: err(q) <= 2e-3 + 20 * sens(q), sens = the query's own movement under the probes, for all but
     #       2 % of the queries (a different rounding realisation can hit a query the probes happened to miss).
-    import torch.nn.functional as RealF
-
-    class _F16Operands:
-        def __getattr__(self, k):
-            return getattr(RealF, k)
-
-        def linear(self, a, w, b=None):
-            return RealF.linear(a.half().float(), w.half().float(), b)
-
-        def conv2d(self, a, w, b=None, **kw):
-            return RealF.conv2d(a.half().float(), w.half().float(), b, **kw)
-
-    def probe(sd_, proxy):
+    def probe(sd_, f16_operands):
         pst = {"force_topk": st["topk"]}
-        gdino_ref.F = proxy
-        try:
+        with gdino_ref.f16_operands() if f16_operands else contextlib.nullcontext():
             pl, pb = gdino_ref.detector_forward(sd_, oc, x[None], text, sm, pid, stages=pst)
-        finally:
-            gdino_ref.F = RealF
         return ((pb[0] - ref_boxes[0]).abs().max(-1)[0],
                 (pl[0] - ref_logits[0]).abs().max(-1)[0] / ref_logits.abs().max())
 
     sd16 = {k: (v.half().float() if v.dim() >= 2 else v) for k, v in sd.items()}
-    eb, el = probe(sd, _F16Operands())              # the yardstick: f16 operands everywhere
-    wb, wl = probe(sd16, RealF)                     # second probe: f16 weights only
+    eb, el = probe(sd, True)                        # the yardstick: f16 operands everywhere
+    wb, wl = probe(sd16, False)                     # second probe: f16 weights only
     for name, mine, emul in (("box", d, eb), ("logit", dl, el)):
         for qt in (0.5, 0.75, 0.9, 0.99, 1.0):
             hq, eq = mine.quantile(qt).item(), emul.quantile(qt).item()
@@ -264,23 +250,8 @@ def test_detect_threshold_path_matches_oracle_postprocess(dev, small_dino):
     flips = (keep_hip != keep_ref)
     # yardstick: the fp32 oracle itself with f16-rounded operands (the stated arithmetic) - how many queries cross the
     # threshold there, and from how far away
-    import torch.nn.functional as RealF
-
-    class _F16Operands:
-        def __getattr__(self, k):
-            return getattr(RealF, k)
-
-        def linear(self, a, w, b=None):
-            return RealF.linear(a.half().float(), w.half().float(), b)
-
-        def conv2d(self, a, w, b=None, **kw):
-            return RealF.conv2d(a.half().float(), w.half().float(), b, **kw)
-
-    gdino_ref.F = _F16Operands()
-    try:
+    with gdino_ref.f16_operands():
         el, _ = gdino_ref.detector_forward(sd, oc, x[None], text, sm, pid, stages={"force_topk": st["topk"].cpu()})
-    finally:
-        gdino_ref.F = RealF
     eflips = (el[0].sigmoid().max(-1)[0] > thr) != keep_ref
     far = lambda f: (score - thr).abs()[f].max().item() if f.any() else 0.0
     print(f"flipped queries: HIP {int(flips.sum())} (farthest {far(flips):.4f} from the threshold), emulated-f16 oracle "
