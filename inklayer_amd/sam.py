@@ -168,6 +168,21 @@ class ResizeLongestSide:
         return self.apply_coords_torch(boxes.reshape(-1, 2, 2), original_size).reshape(-1, 4)
 
 
+def window_rows(B: int, g: int, ws: int) -> torch.Tensor:
+    """The window gather/scatter map (window_partition / window_unpartition, image_encoder.py:243-289) of B images of
+    g x g tokens: int32 [B * n * n * ws * ws] (n = ceil(g / ws)), token i of window w of image b at entry
+    (b * n * n + w) * ws * ws + i holds its token row b * g * g + y * g + x, or -1 for window padding."""
+    nwin = -(-g // ws)
+    Mw = nwin * nwin * ws * ws
+    r = torch.arange(B * Mw)
+    b, rr = r // Mw, r % Mw
+    win, pos = rr // (ws * ws), rr % (ws * ws)
+    y = (win // nwin) * ws + pos // ws
+    x = (win % nwin) * ws + pos % ws
+    m = torch.where((y < g) & (x < g), b * g * g + y * g + x, torch.full_like(r, -1))
+    return m.to(torch.int32)
+
+
 def _to_dev_async(t: torch.Tensor, dev) -> torch.Tensor:
     """Small host tensor -> device through pinned memory, non-blocking.  A pageable `.to(dev)` makes the host wait
     until the stream has drained (here: the whole image encoder) before it can queue the decoder's launches."""
@@ -433,14 +448,7 @@ class SamEngine:
         self.Mw = Mw
         self._enc_graphs = LRU(self.graph_cache_size)
         self._enc_seen: Dict[int, int] = {}
-        # window gather/scatter map (window_partition / window_unpartition, image_encoder.py:243-289)
-        r = torch.arange(B * Mw)
-        b, rr = r // Mw, r % Mw
-        win, pos = rr // (ws * ws), rr % (ws * ws)
-        y = (win // nwin) * ws + pos // ws
-        x = (win % nwin) * ws + pos % ws
-        m = torch.where((y < g) & (x < g), b * T + y * g + x, torch.full_like(r, -1))
-        self.win_map = m.to(torch.int32).to(dev)
+        self.win_map = window_rows(B, g, ws).to(dev)
         P = cfg.patch_size
         e = lambda *s, dt=F16: torch.empty(s, device=dev, dtype=dt)
         self.buf_patches = e(B * T, 3 * P * P * (3 if self.precise_tail else 1))

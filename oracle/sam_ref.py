@@ -7,6 +7,7 @@ Pinned against the reference modules by tests/golden/sam_small.npz
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Sequence, Tuple
@@ -16,6 +17,32 @@ import torch
 import torch.nn.functional as F
 
 SD = Dict[str, torch.Tensor]
+_REAL_F = F
+
+
+class F16Operands:
+    """torch.nn.functional with both operands of every linear / conv2d rounded to f16 (what the HIP image encoder
+    does: f16 weights and activations, wider accumulation), computed in the caller's dtype."""
+
+    def __getattr__(self, k):
+        return getattr(_REAL_F, k)
+
+    def linear(self, a, w, b=None):
+        return _REAL_F.linear(a.half().to(a.dtype), w.half().to(w.dtype), b)
+
+    def conv2d(self, a, w, b=None, **kw):
+        return _REAL_F.conv2d(a.half().to(a.dtype), w.half().to(w.dtype), b, **kw)
+
+
+@contextlib.contextmanager
+def f16_operands():
+    """Run this module's functions with F16Operands in place of torch.nn.functional (the tests' yardstick)."""
+    global F
+    F = F16Operands()
+    try:
+        yield
+    finally:
+        F = _REAL_F
 
 
 @dataclass
