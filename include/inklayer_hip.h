@@ -72,14 +72,15 @@ typedef struct InkGemm {
 #define INK_ACT_GELU 1
 #define INK_ACT_RELU 2
 int ink_gemm_f16(const InkGemm* p, void* stream);
-/* Tuning knob (tools/gemm_sweep.py): force tile variant v >= 0 (gm * 100 + variant, gm = tile-order group size) for
- * every following ink_gemm_f16 call; -1 restores the built-in shape heuristic (-2: the same heuristic restricted to
- * one-tile-per-workgroup kernels, for whole-step A/B runs).  Results are identical across variants up to f32
- * summation order.  A variant that cannot take a call's form (e.g. 54 / 55: plain epilogues of the 256x320 tile only)
- * makes ink_gemm_f16 return INK_ERR_ARG.  Process-wide, not thread-safe, never set by the product path. */
+/* Test hook: force one of the heuristic's tile families for every following ink_gemm_f16 call (0 = 128x128,
+ * 10 = 16-wave 256x256, 45 = ping-pong 256x320, each with the tile order the heuristic gives it); -1 restores the
+ * built-in shape heuristic.  Any other v returns INK_ERR_ARG.  Results are identical across families up to f32
+ * summation order; K % 64 != 0 always takes the 128x128x32 tile, and a family that cannot take a call's form makes
+ * ink_gemm_f16 return INK_ERR_ARG.  Process-wide, not thread-safe, never set by the product path. */
 int ink_gemm_set_variant(int32_t v);
-/* Which tile variant the built-in heuristic picks for (M,N,K): 10 = 256x256x64 / 16 waves (the dominant kernel),
- * 0 = 128x128x64 / 4 waves, 32 = 128x128x32 (K % 64 != 0).  Pure host function, used by bench.py's roofline. */
+/* Which tile variant the built-in heuristic picks for (M,N,K): 45 = 256x320 ping-pong (the dominant kernel),
+ * 10 = 256x256x64 / 16 waves, 0 = 128x128x64 / 4 waves, 32 = 128x128x32 (K % 64 != 0).  Pure host function, used by
+ * bench.py's roofline. */
 int ink_gemm_query_variant(int32_t M, int32_t N, int32_t K);
 int ink_gemm_query_stats_chunk(int32_t M, int32_t N, int32_t K);
 

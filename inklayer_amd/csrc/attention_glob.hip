@@ -21,7 +21,7 @@
 //   * O rows leave through LDS as 160-B row segments.
 // The 16 query tiles of an (image, head) run on ONE XCD, adjacent in time (xcd_remap): K/V is fetched from HBM once.
 // Measured (same-box A/B, tools/attn_time.py): 997 us per launch at B = 8 against 1058 us for the 2-waves-per-SIMD form
-// (692 vs 650 TFLOP/s).  Stamps (tools/glob_stamps.py): a key tile takes ~4300 cycles, of which the MFMA + LDS + load
+// (692 vs 650 TFLOP/s).  Stamps (commit 8926174): a key tile takes ~4300 cycles, of which the MFMA + LDS + load
 // skeleton alone takes 2050 (the softmax fillers compiled out) - the fillers (est. 1250-1750 cycles of VALU issue per
 // tile, two v_exp per MFMA gap) ADD to the skeleton instead of hiding in it.  The guide's rule is one transcendental
 // per gap; 64 exps per tile do not fit 44 gaps, so the kernel is bound by VALU/transcendental issue, not by the MFMA
@@ -86,18 +86,6 @@ constexpr int OROW = 176;                              // output staging rows (r
 static_assert(4 * 64 * OROW <= 2 * TILE, "the output tiles fit the K/V buffers");
 constexpr float NEG = -1e30f;
 constexpr float THR = 12.0f;
-
-#ifdef INK_ABLATION
-// measurement build only (tools/glob_stamps.py): s_memtime stamps of workgroup 0, [wave][tile 8..23][8]
-__device__ unsigned long long g_glob_stamps[4 * 16 * 8];
-#define GSTAMP(i)                                                                                   \
-  do {                                                                                              \
-    if (blockIdx.x == 0 && lane == 0 && t >= 8 && t < 24)                                           \
-      g_glob_stamps[(wave * 16 + (t - 8)) * 8 + (i)] = __builtin_amdgcn_s_memtime();                \
-  } while (0)
-#else
-#define GSTAMP(i)
-#endif
 
 struct Sub {
   f16x8 qf[NQK];     // Q^T fragments (B operand)
@@ -331,7 +319,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     constexpr int PAR = decltype(PAR_)::value;
     constexpr bool FIRST = decltype(FIRST_)::value;
     float rhA1 = 0.f, rhB1 = 0.f;
-    GSTAMP(0);
     if constexpr (FIRST) {
       // pipeline fill: S_B(0) || softmax_A(0) first half, then its second half alone
       static_for<0, 10>([&](auto g_) {
@@ -361,7 +348,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         if constexpr (g >= 8) read_rw(B, qlB, g - 8);             // (B's scores of tile t-1 are consumed: unit 4)
         GAP();
       });
-      GSTAMP(1);
       // S_B(t)  ||  softmax_A(t), second half; V^T fragments of tile t; loads 3, 4
       static_for<0, 10>([&](auto g_) {
         constexpr int g = decltype(g_)::value;
@@ -376,11 +362,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
     // every wave has read tile t out of buffer PAR (K fragments one tile ago, V^T just now), and tile t+1 - written to
     // buffer 1 - PAR during the previous tile - is complete
-    GSTAMP(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    GSTAMP(3);
     // PV_A(t)  ||  softmax_B(t), first half; K fragments of tile t+1; tile t+2: registers -> buffer PAR
     static_for<0, 12>([&](auto g_) {
       constexpr int g = decltype(g_)::value;
@@ -392,7 +376,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       if constexpr (g >= 8) read_rw(A, qlA, g - 8);               // (A's scores of tile t are consumed: unit 2)
       GAP();
     });
-    GSTAMP(4);
     // S_A(t+1)  ||  softmax_B(t), second half
     static_for<0, 10>([&](auto g_) {
       constexpr int g = decltype(g_)::value;
@@ -404,7 +387,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     });
     rhA = rhA1;
     rhB = rhB1;
-    GSTAMP(5);
   };
 
   tile_iter(0, ic<0>{}, std::true_type{});
@@ -464,9 +446,3 @@ __attribute__((visibility("hidden"))) int ink_glob4_attn_launch(const InkAttn& p
   }
   return ink_launch_status();
 }
-
-#ifdef INK_ABLATION
-extern "C" int ink_glob4_read_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_glob_stamps), sizeof(g_glob_stamps)) == hipSuccess ? INK_OK : INK_ERR_LAUNCH;
-}
-#endif

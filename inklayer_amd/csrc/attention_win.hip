@@ -32,9 +32,10 @@
 //     with 4 rotating registers every piece waits out its latency: 297 us).
 //   * staging map: thread t < 250 owns chunk t % 10 of keys t / 10 + 25 it (it < 9): its LDS and table addresses
 //     differ by constants.
-// Measured (tools/attn_time.py, tools/win_stamps.py): 122 us per launch at B = 8 (336 MB of q,k,v,o: 2.75 TB/s = 34 % of
-// 8 TB/s) against 172 us for the 2-waves-per-SIMD form; per block ~17 000 cycles of which 3 x 2450 are the tiles
-// (52 MFMAs each: 47 cycles per gap, the gap's VALU + LDS + MFMA issue, not the 32 of the MFMA pipe).
+// Measured (tools/attn_time.py; cycle stamps of the instrumented build at commit 8926174): 122 us per launch at B = 8
+// (336 MB of q,k,v,o: 2.75 TB/s = 34 % of 8 TB/s) against 172 us for the 2-waves-per-SIMD form; per block ~17 000
+// cycles of which 3 x 2450 are the tiles (52 MFMAs each: 47 cycles per gap, the gap's VALU + LDS + MFMA issue, not the
+// 32 of the MFMA pipe).
 #include <type_traits>
 #include "common.h"
 #include "../../include/inklayer_hip.h"
@@ -87,38 +88,11 @@ constexpr int HD = 80, NT = 256, NQKB = 5, NQK = 7, NB = 3, CH = 10;
 constexpr int KROW = 240, VROW = 192, ROWS = 232;     // K' rows: k | one-hot(kh, kw) | pad; V rows: v | ones-column | pad
 constexpr int SKEYS = 25, SIT = 9, STHR = SKEYS * CH;
 constexpr int XROW = 176;                             // wave-private staging tile: 64 O rows of 160 B
-#ifndef INK_EXP_LDS_SLACK
-#define INK_EXP_LDS_SLACK 0          // (experiment, tools/race_variants.sh: unused bytes requested after the kernel's own)
-#endif
-constexpr int LDS_BYTES = ROWS * KROW + ROWS * VROW + 256 * 4 + 4 * 64 * XROW + 4 * 64 * 4 + INK_EXP_LDS_SLACK;
+constexpr int LDS_BYTES = ROWS * KROW + ROWS * VROW + 256 * 4 + 4 * 64 * XROW + 4 * 64 * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-#ifndef INK_WIN_DROP
-#define INK_WIN_DROP 0x80000000u       // offset of a store the buffer bounds check drops (= the descriptor's num_records)
-#endif
+constexpr uint32_t DROP = 0x80000000u;   // offset of a store the buffer bounds check drops (= the descriptor's num_records)
 constexpr float NEG = -1e30f;
-constexpr float THR = 12.0f;
-// schedule knobs of `vm` (tools/win_variants.sh builds alternatives for same-box A/B runs)
-#ifndef INK_WIN_KV_STEP
-#define INK_WIN_KV_STEP 4
-#endif
-#ifndef INK_WIN_ST_STEP
-#define INK_WIN_ST_STEP 3
-#endif
-#ifndef INK_WIN_QA_EARLY
-#define INK_WIN_QA_EARLY 0
-#endif          // deferred max: rescale when a row's max grew by more than 2^THR
-
-#ifdef INK_ABLATION
-// measurement build only (tools/win_stamps.py): s_memtime stamps of workgroup 0's waves, [wave][block][16]
-__device__ unsigned long long g_win_stamps[4 * 16 * 16];
-#define STAMP(i)                                                                              \
-  do {                                                                                        \
-    if (blockIdx.x == 0 && lane == 0 && nstamp < 16)                                          \
-      g_win_stamps[(wave * 16 + nstamp) * 16 + (i)] = __builtin_amdgcn_s_memtime();           \
-  } while (0)
-#else
-#define STAMP(i)
-#endif
+constexpr float THR = 12.0f;          // deferred max: rescale when a row's max grew by more than 2^THR
 
 // One 32-query subtile's softmax state and operands.
 struct Sub {
@@ -262,13 +236,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // those kernels read zeros in one register of one quarter-wave (groupnorm_apply_kernel: gamma.z of lanes 48..63 in
   // 48 of 48 runs; the detector's boxes wrong in a third of back-to-back two-stream steps).  No store of this kernel
   // leaves its output (tools/win_canary.py), its own results never change, the buffer-store bounds trick and the LDS
-  // size are not involved (variants built by tools/race_variants.sh); with the full claim: 0 of 80.
-#ifndef INK_EXP_CLAIM_AGPR         // (experiment switch of tools/race_variants.sh: claim up to another AGPR; 180 = old behaviour)
-#define INK_EXP_CLAIM_AGPR 255
-#endif
-#define INK_STR2(x) #x
-#define INK_STR(x) INK_STR2(x)
-  asm volatile("v_accvgpr_write_b32 a" INK_STR(INK_EXP_CLAIM_AGPR) ", %0" ::"v"(0) : "a" INK_STR(INK_EXP_CLAIM_AGPR));
+  // size are not involved; with the full claim: 0 of 80.
+  asm volatile("v_accvgpr_write_b32 a255, %0" ::"v"(0) : "a255");
   char* sK = smem;
   char* sV = smem + ROWS * KROW;
   int* sT = (int*)(smem + ROWS * KROW + ROWS * VROW);    // token rows of the window being fetched, [256]
@@ -397,7 +366,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   int rt = fetch_row(blk + 1 < blk_end ? blk + 1 : last);
   load_q(blk, qrowA, qcA, A);
   load_q(blk, qrowB, qcB, B);
-  myOoff[lane] = INK_WIN_DROP;                          // (no output rows staged yet: the first block's stores are dropped)
+  myOoff[lane] = DROP;                                  // (no output rows staged yet: the first block's stores are dropped)
 
   const float c = p.scale * 1.44269504088896340736f;
   const int koff0 = lq * KROW + hh * 16;
@@ -410,17 +379,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // (hipcc merges the memory-counter state of the loop entry with the back edge's and waits for the smaller count:
   // ten dropped stores here give the entry the block loop's own issue order - rows, Q', stores - so the waits at
   // the loop top count the stores of the previous block instead of draining them)
-#ifndef INK_EXP_GLOBAL_STORES
 #pragma unroll
   for (int i = 0; i < 10; ++i)
-    __builtin_amdgcn_raw_buffer_store_b64((i32x2){0, 0}, orsrc, INK_WIN_DROP, 0, 0);
-#endif
+    __builtin_amdgcn_raw_buffer_store_b64((i32x2){0, 0}, orsrc, DROP, 0, 0);
 
-  int nstamp = 0;
-  (void)nstamp;
   for (; blk < blk_end; ++blk) {
     const int b = blk / p.n_heads, h = blk - b * p.n_heads;
-    STAMP(0);
     const bool okA = qiA < p.n_q && (!TOK || qrowA >= 0);    // window padding: nothing to compute, nothing to store
     const bool okB = qiB < p.n_q && (!TOK || qrowB >= 0);
     __syncthreads();                                          // every wave has finished reading block blk - 1
@@ -430,15 +394,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       *(f16x8*)(wV + it * SKEYS * VROW) = va[it];
     }
     sT[tid] = rt;
-    STAMP(1);
     __syncthreads();
-    STAMP(2);
     const int n1 = blk + 1 < blk_end ? blk + 1 : last, n2 = blk + 2 < blk_end ? blk + 2 : last;
     const int qrow1A = query_row(n1, qcA), qrow1B = query_row(n1, qcB);
     read_rows();
     lane_x = lane;
     asm volatile("" : "+v"(lane_x));
-    STAMP(3);
 
 #pragma unroll
     for (int i = 0; i < NB; ++i)
@@ -474,14 +435,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       const int idx = j * 64 + lane_x, row = idx / CH, ch = idx - row * CH;
       ov[j & 1] = *(const f16x8*)(myX + row * XROW + ch * 16);
       const uint32_t off = myOoff[row];
-      ooff[j & 1] = off == INK_WIN_DROP ? off : off + (uint32_t)(ch * 16);
+      ooff[j & 1] = off == DROP ? off : off + (uint32_t)(ch * 16);
     };
     auto xo_issue = [&](int j) {               // ... -> O (read one slot earlier: no LDS round trip inside a gap)
-#ifdef INK_EXP_GLOBAL_STORES       // (experiment of tools/race_variants.sh: masked global stores instead of buffer stores)
-      if (ooff[j & 1] < 0x80000000u) *(i32x4*)((char*)p.O + ooff[j & 1]) = __builtin_bit_cast(i32x4, ov[j & 1]);
-#else
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, ov[j & 1]), orsrc, ooff[j & 1], 0, 0);
-#endif
     };
     // The block's vector-memory instructions, spread over its 166 MFMA gaps (G = gap number in the block, a
     // compile-time constant after unrolling).  Back to back they overflow the CU's vector-memory queue (4 waves x 19
@@ -494,7 +451,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     auto vm = [&](auto G_) {
       constexpr int G = decltype(G_)::value;
       if constexpr (G == 0) xo_read(0);
-      constexpr int ST = INK_WIN_ST_STEP, KS = INK_WIN_KV_STEP, KV0 = 2 + ST * 9 + 2;
+      constexpr int ST = 3, KS = 4, KV0 = 2 + ST * 9 + 2;
       static_assert(KV0 + KS * 17 < 140, "the K / V loads end before the table row load");
       if constexpr (G >= 2 && G <= 2 + ST * 9 && (G - 2) % ST == 0) {
         constexpr int i = (G - 2) / ST;
@@ -503,10 +460,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       }
       if constexpr (G >= KV0 && G <= KV0 + KS * 17 && (G - KV0) % KS == 0) fetch_kv_one(n1, (G - KV0) / KS);
       if constexpr (G == 140) rt = fetch_row(n2);
-      if constexpr (INK_WIN_QA_EARLY) {       // A's fragments are dead after its tail S unit (G 140..146)
-        if constexpr (G >= 147 && G <= 153) load_q_piece(n1, qrow1A, qcA, A, G - 147);
-        if constexpr (G >= 154 && G <= 160) load_q_piece(n1, qrow1B, qcB, B, G - 154);
-      } else if constexpr (G >= 154 && G <= 165) {
+      if constexpr (G >= 154 && G <= 165) {
         constexpr int k = G - 154;
         if constexpr (k < NQK) load_q_piece(n1, qrow1A, qcA, A, k); else load_q_piece(n1, qrow1B, qcB, B, k - NQK);
       }
@@ -522,7 +476,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
       for (int j = 0; j < 14; ++j) s_mfma(j, kfa, kfb, A);
       GAP();
-      STAMP(4);
       static_for<0, 3>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
         if constexpr (t == 0) {
@@ -582,10 +535,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
           vm(ic<t * 52 + 36 + g>{});
           GAP();
         });
-        STAMP(5 + t);
       });
     }
-    STAMP(8);
     {
       // PV_B(2)  ||  tail softmax of A; tail V fragments
       static_for<0, 12>([&](auto g_) {
@@ -621,17 +572,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
           }
         }
       const uint32_t o_row = TOK ? (uint32_t)qrow : (uint32_t)(b * p.n_q + qi);
-      if (hh == 0) myOoff[row0 + lq] = ok ? (o_row * (uint32_t)p.ldo + (uint32_t)(h * HD)) * 2u : INK_WIN_DROP;
+      if (hh == 0) myOoff[row0 + lq] = ok ? (o_row * (uint32_t)p.ldo + (uint32_t)(h * HD)) * 2u : DROP;
     };
-    STAMP(9);
-    if constexpr (!INK_WIN_QA_EARLY) {
-      load_q_piece(n1, qrow1B, qcB, B, 5);
-      load_q_piece(n1, qrow1B, qcB, B, 6);
-    }
+    load_q_piece(n1, qrow1B, qcB, B, 5);
+    load_q_piece(n1, qrow1B, qcB, B, 6);
     stage_o(A, okA, qrowA, qiA, 0);
     stage_o(B, okB, qrowB, qiB, 32);
-    STAMP(10);
-    ++nstamp;
     qrowA = qrow1A;
     qrowB = qrow1B;
   }
@@ -642,12 +588,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const int idx = j * 64 + lane, row = idx / CH, ch = idx - row * CH;
     const f16x8 v = *(const f16x8*)(myX + row * XROW + ch * 16);
     const uint32_t off = myOoff[row];
-#ifdef INK_EXP_GLOBAL_STORES
-    if (off != INK_WIN_DROP) *(i32x4b*)((char*)p.O + off + (uint32_t)(ch * 16)) = __builtin_bit_cast(i32x4b, v);
-#else
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4b, v), orsrc,
-                                           off == INK_WIN_DROP ? off : off + (uint32_t)(ch * 16), 0, 0);
-#endif
+                                           off == DROP ? off : off + (uint32_t)(ch * 16), 0, 0);
   }
 }
 
@@ -669,9 +611,3 @@ __attribute__((visibility("hidden"))) int ink_win4_attn_launch(const InkAttn& p,
   }
   return ink_launch_status();
 }
-
-#ifdef INK_ABLATION
-extern "C" int ink_win4_read_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_win_stamps), sizeof(g_win_stamps)) == hipSuccess ? INK_OK : INK_ERR_LAUNCH;
-}
-#endif

@@ -41,10 +41,7 @@ constexpr int MAX_HID = 2048;
 constexpr int OROW = C * 4 + 16;                // epilogue staging row (f32) + pad
 constexpr int PAR_BYTES = 5 * C * 4;             // LayerNorm / bias vectors next to the weight buffers: pre_g, pre_be, b2, ln_g, ln_b
 constexpr int LDS_BYTES = 2 * CHUNK + PAR_BYTES;
-#ifndef INK_FFN_DEPTH
-#define INK_FFN_DEPTH 6
-#endif
-constexpr int DEPTH = INK_FFN_DEPTH;            // fragment reads in flight ahead of the MFMA that consumes them
+constexpr int DEPTH = 6;                        // fragment reads in flight ahead of the MFMA that consumes them
 constexpr int NPRE = 2;                         // chunks of the optional preceding [256 -> 256] projection (128 blocks + padding)
 constexpr int NSLOT = (NBLK + 3) / 4;           // LDS-DMA pieces per wave and chunk (17; piece index clamped to NBLK - 1)
 static_assert(4 * 32 * OROW <= 2 * CHUNK, "epilogue staging fits the (then free) weight buffers");
@@ -315,14 +312,8 @@ __global__ __launch_bounds__(256) void ffn256_fused_kernel(const f16* __restrict
     f16x8 hf[HC / 16];
     static_for<0, NBLK>([&](auto ii) {
       constexpr int i = decltype(ii)::value;
-#ifndef INK_FFN_NOREAD
       if constexpr (i + DEPTH < NBLK) read(ic<i + DEPTH>{});
-#endif
-#ifndef INK_FFN_NOREAD
       wait_frag<(NBLK - 1 - i < DEPTH ? NBLK - 1 - i : DEPTH)>(fr[i % (DEPTH + 1)]);
-#else
-      wait_frag<0>(fr[i % (DEPTH + 1)]);
-#endif
       if constexpr (i < W1_BLKS) {
         constexpr int s = i / 2, jt = i % 2;
         h[jt] = mfma32(fr[i % (DEPTH + 1)], xf[s], s == 0 ? zero : h[jt]);
@@ -335,9 +326,7 @@ __global__ __launch_bounds__(256) void ffn256_fused_kernel(const f16* __restrict
         }
         y[nt] = mfma32(fr[i % (DEPTH + 1)], hf[s], y[nt]);
       }
-#ifndef INK_FFN_NODMA          // (timing experiments of tools/ffn_variants.sh: wrong results)
       if constexpr (i % 4 == 1) stage((c + 1) & 1, cn, i / 4);
-#endif
     });
   }
 

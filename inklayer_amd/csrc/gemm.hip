@@ -1,8 +1,8 @@
 // Dense projection kernels for gfx950 (MI355X): C = epilogue(A[M,K] * W[N,K]^T), f16 operands, f32 accumulate.
 //
 // Two kernel families share one accumulator set-up / epilogue (init_wave_tile, store_wave_tile):
-//   gemm_f16_nt_pp  ping-pong: 256x256 or 256x320 tile, 8 waves in two groups staggered by one barrier, ring of
-//                   K32 granules with counted vmcnt - the SAM ViT-H projections (see its comment);
+//   gemm_f16_nt_pp  ping-pong: 256x320 tile, 8 waves in two groups staggered by one barrier, ring of four K32
+//                   granules with counted vmcnt - the SAM ViT-H projections (see its comment);
 //   gemm_f16_nt     generic BMxBN tile, WMxWN waves of (BM/WM)x(BN/WN), two LDS stages with one drain + barrier per
 //                   K-tile - 16-wave 256x256 for the other large shapes, 128x128 (K step 64 or 32) for the rest.
 // Common to both (cdna_hip_programming.md §5):
@@ -15,9 +15,8 @@
 //     M-tiles x all N-tiles at a time, and re-reads its A / W panels from L2;
 //   - epilogue (fused, f32): +bias, GELU/ReLU, *col_scale, +residual (preloaded into the accumulators for linear
 //     GEMMs), optional row scatter (window-unpartition / crop / un-shift), f32 or f16 store as whole row segments.
-// Variant choice: ink_gemm_query_variant; everything else in the switch of ink_gemm_f16 is a measurement build.
+// Tile choice: ink_gemm_query_variant (shape heuristic); ink_gemm_set_variant forces one of its tile families (tests).
 #include <stdlib.h>
-#include <type_traits>
 
 #include "common.h"
 #include "../../include/inklayer_hip.h"
@@ -42,8 +41,8 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // Loads and stores share vmcnt and retire in issue order in the counter, so a load issued AFTER a store can only
 // be waited for with vmcnt(0) - i.e. by waiting for that store to reach memory (and the compiler has to assume
 // the worst over all paths, so "counted" waits degrade to 0 as soon as a store may be skipped).  Measured with
-// s_memrealtime stamps (tools/gemm_stamps.py): with the row_map / residual / bias loads inside the slab loop each
-// of the 8 slabs of a 256x256 tile paid a full store round trip, 7.5 us per tile against a 31 us main loop.
+// s_memrealtime stamps (instrumented build, commit 8926174): with the row_map / residual / bias loads inside the slab
+// loop each of the 8 slabs of a 256x256 tile paid a full store round trip, 7.5 us per tile against a 31 us main loop.
 // So the slab loop contains NO load:
 //   * the residual of the linear case (no activation, no layer scale - every large GEMM of the pipeline) is
 //     loaded straight into the accumulators before the K loop, row-mapped, and the MFMAs accumulate on top of it
@@ -158,8 +157,8 @@ __device__ __forceinline__ void ln_rows_prologue(const InkGemm& p, float2* strip
 // p.stats_out: per output row and per wave-tile column chunk the partial (sum, sum of squares) of the final values -
 // the LayerNorm statistics of the NEXT projection (ln_rows_prologue), computed here for free.
 // p.ln_stats: this projection is itself a folded LayerNorm + Linear (see ln_rows_prologue); `strip` holds its rows.
-// BIAS = false: the caller has added the bias already (add_bias_wave_tile) - the persistent kernel puts the next tile's
-// pipeline fill between the bias loads and the stores, and then nothing in here loads from global memory.
+// add_bias_wave_tile: the bias add (a function of its own: with its loop written inline, hipcc schedules the epilogue's
+// bias loads differently).
 template <int TM, int TN>
 __device__ __forceinline__ void add_bias_wave_tile(f32x4 (&acc)[TM][TN], const InkGemm& p, int nw, int lane) {
   const int fq = lane >> 4;
@@ -173,7 +172,7 @@ __device__ __forceinline__ void add_bias_wave_tile(f32x4 (&acc)[TM][TN], const I
   }
 }
 
-template <int TM, int TN, int OUT, int MODE = -1, bool LNF = false, bool BIAS = true>
+template <int TM, int TN, int OUT, int MODE = -1, bool LNF = false>
 __device__ __forceinline__ void store_wave_tile(f32x4 (&acc)[TM][TN], const InkGemm& p, char* er,
                                                 const int (&rows)[TM], int nw, int lane, const float2* strip = nullptr) {
   constexpr bool F16O = OUT == 1;
@@ -213,7 +212,7 @@ __device__ __forceinline__ void store_wave_tile(f32x4 (&acc)[TM][TN], const InkG
       }
       __builtin_amdgcn_sched_barrier(0);                       // one column group at a time: 8 + 16 live values
     }
-  } else if (BIAS) {
+  } else {
     add_bias_wave_tile<TM, TN>(acc, p, nw, lane);
   }
 
@@ -309,38 +308,10 @@ __device__ __forceinline__ void store_wave_tile(f32x4 (&acc)[TM][TN], const InkG
   }
 }
 
-// Generic tile: BM x BN output per workgroup, WM x WN waves (each (BM/WM) x (BN/WN)), K step BK,
-// NS LDS stages.  NS == 2: one K-tile in flight, plain __syncthreads (drains the DMA).
-// NS >= 3: NS-1 K-tiles in flight behind a COUNTED s_waitcnt vmcnt(N) + raw s_barrier
-// (cdna_hip_programming.md §5 "Pipelining across barriers"): the wait that retires tile kt comes
-// before the barrier, the reads of tile kt after it, and the buffer that is re-filled is the one read
-// in the previous iteration (every wave has passed this iteration's barrier, i.e. finished those reads).
-// EXT: the kernel also carries the ABI-4 forms (split-f16 output + row statistics, folded LayerNorm); only the 128x128
-// tiles are built with it - the 16-wave 256x256 tile has 128 VGPRs per lane and no room for them.
-template <int BM, int BN, int BK, int WM, int WN, int NS, int ABL = 0, bool EXT = false>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_f16_nt(InkGemm p, int group_m) {
-  constexpr int NT = WM * WN * 64;
-  constexpr int CPR = BK / 8;          // 16-B chunks per tile row
-  constexpr int ROWB = BK * 2;         // bytes per tile row
-  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB;
-  constexpr int STAGE = TILE_A + TILE_W;
-  constexpr int IT_A = (BM * CPR) / NT, IT_W = (BN * CPR) / NT;
-  constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
-  constexpr int LOADS = IT_A + IT_W;   // DMA instructions per thread per stage
-  static_assert((BM * CPR) % NT == 0 && (BN * CPR) % NT == 0, "tile/threads mismatch");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-
-  const int ntn = (p.N + BN - 1) / BN;
-  const int ntm = (p.M + BM - 1) / BM;
-  const int id = xcd_remap(blockIdx.x, ntm * ntn);
-  // grouped order inside the XCD-contiguous id space: GM consecutive M-tiles x all N-tiles, M fastest, so the
-  // ~32 tiles an XCD runs concurrently share GM A-panels and 32/GM W-panels (L2 = 4 MiB per XCD)
-  int mt, nt;
+// Tile coordinates of workgroup id (after xcd_remap) in the grouped order inside the XCD-contiguous id space:
+// group_m consecutive M-tiles x all N-tiles, M fastest, so the ~32 tiles an XCD runs concurrently share group_m
+// A-panels and 32/group_m W-panels (L2 = 4 MiB per XCD); group_m = 1: row-major.
+__device__ __forceinline__ void tile_of(int id, int ntm, int ntn, int group_m, int& mt, int& nt) {
   if (group_m > 1) {
     const int per = group_m * ntn;
     const int first = (id / per) * group_m;
@@ -351,6 +322,34 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_f16_nt(InkGemm p, int group
     mt = id / ntn;
     nt = id % ntn;
   }
+}
+
+// Generic tile: BM x BN output per workgroup, WM x WN waves (each (BM/WM) x (BN/WN)), K step BK, NS = 2 LDS stages:
+// one K-tile in flight, plain __syncthreads (drains the DMA).
+// EXT: the kernel also carries the ABI-4 forms (split-f16 output + row statistics, folded LayerNorm); only the 128x128
+// tiles are built with it - the 16-wave 256x256 tile has 128 VGPRs per lane and no room for them.
+constexpr int NS = 2;
+template <int BM, int BN, int BK, int WM, int WN, bool EXT>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_f16_nt(InkGemm p, int group_m) {
+  constexpr int NT = WM * WN * 64;
+  constexpr int CPR = BK / 8;          // 16-B chunks per tile row
+  constexpr int ROWB = BK * 2;         // bytes per tile row
+  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB;
+  constexpr int STAGE = TILE_A + TILE_W;
+  constexpr int IT_A = (BM * CPR) / NT, IT_W = (BN * CPR) / NT;
+  constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
+  static_assert((BM * CPR) % NT == 0 && (BN * CPR) % NT == 0, "tile/threads mismatch");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+
+  const int ntn = (p.N + BN - 1) / BN;
+  const int ntm = (p.M + BM - 1) / BM;
+  int mt, nt;
+  tile_of(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, group_m, mt, nt);
   const int m0 = mt * BM;
   const int n0 = nt * BN;
 
@@ -420,54 +419,22 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_f16_nt(InkGemm p, int group
     }
   };
 
-  if constexpr (NS == 2) {
-    stage(0, 0);
-    if (EXT && p.res_hi) {
-      init_wave_tile<TM, TN, true>(acc, p, rows, n0 + wn * (BN / WN), lane);
-    } else {
-      init_wave_tile<TM, TN>(acc, p, rows, n0 + wn * (BN / WN), lane);
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-      // the LDS-DMA of tile kt is tracked by vmcnt only: drain it EXPLICITLY before the barrier (whether
-      // __syncthreads() alone emits the vmcnt wait depends on what else the compiler sees in flight)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (kt + 1 < nk && (ABL != 1 || kt == 0)) stage((kt + 1) & 1, kt + 1);
-      if (ABL != 2 || kt + 1 == nk) compute(kt & 1);
-    }
+  stage(0, 0);
+  if (EXT && p.res_hi) {
+    init_wave_tile<TM, TN, true>(acc, p, rows, n0 + wn * (BN / WN), lane);
   } else {
-#pragma unroll
-    for (int s = 0; s < NS - 1; ++s)
-      if (s < nk) stage(s, s);
     init_wave_tile<TM, TN>(acc, p, rows, n0 + wn * (BN / WN), lane);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the counted waits below assume only DMA in flight)
-    int cur = 0, nxt = NS - 1;
-    for (int kt = 0; kt < nk; ++kt) {
-      // tiles issued after kt and still wanted in flight: min(NS-2, nk-1-kt)
-      if (kt + NS - 2 < nk) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LOADS) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (kt + NS - 1 < nk) stage(nxt, kt + NS - 1);
-      compute(cur);
-      cur = cur + 1 == NS ? 0 : cur + 1;
-      nxt = nxt + 1 == NS ? 0 : nxt + 1;
-    }
+  }
+  for (int kt = 0; kt < nk; ++kt) {
+    // the LDS-DMA of tile kt is tracked by vmcnt only: drain it EXPLICITLY before the barrier (whether
+    // __syncthreads() alone emits the vmcnt wait depends on what else the compiler sees in flight)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
+    compute(kt & 1);
   }
 
   // ---- epilogue: lane holds C[m = .. + fr][n = .. + 4*fq + 0..3] for each (i,j)
-  if (ABL == 3) {   // ablation: no epilogue (keep the accumulators live)
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (sum == 123.456f) ((float*)p.C)[0] = sum;
-    return;
-  }
   constexpr int WNC = BN / WN;                 // columns of the wave tile
   constexpr int EP = WNC * 4 + 16;             // patch row pitch in bytes (f32 worst case + pad)
   static_assert(WM * WN * 16 * EP <= NS * STAGE, "epilogue patch must fit in the staging LDS");
@@ -489,94 +456,52 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_f16_nt(InkGemm p, int group
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Ping-pong kernel: 256x256 tile, 8 waves = two groups of 4 (group = wave / 4 owns 128 rows; one wave of each
-// group per SIMD), K streamed as a ring of RING granules of 32 (32 KiB each: A 256x32 + W 256x32 f16).
-// The groups run the same program staggered by ONE barrier, so in every slot one group issues its 32 MFMAs
-// while the other reads its 12 fragments from LDS and issues the LDS-DMA of the granule RING-1 ahead:
+// Ping-pong kernel: 256x320 tile, 8 waves = two groups of 4 (group = wave / 4 owns 128 rows, wave = 128 x 80, 160
+// accumulator VGPRs; one wave of each group per SIMD), K streamed as a ring of PP_RING = 4 granules of 32 (36 KiB
+// each: A 256x32 + W 320x32 f16).  The groups run the same program staggered by ONE barrier, so in every slot one
+// group issues its 40 MFMAs while the other reads its fragments from LDS and issues the LDS-DMA of the granule
+// AHEAD = 2 ahead:
 //     slot      2g          2g+1        2g+2
 //     group 0   LOAD(g)     MFMA(g)     LOAD(g+1)
 //     group 1   MFMA(g-1)   LOAD(g)     MFMA(g)
-// Granule g sits in ring slot g % RING; both groups have read it by the end of slot 2g+1, and the DMA that
-// overwrites it (granule g+RING) is issued in slots 2g+2 / 2g+3.  Every wave ends its LOAD slot with a COUNTED
-// vmcnt (RING-2 granules stay in flight) and every slot ends with a raw s_barrier, so a granule is only read after
+// Only four of the eight A fragments are live: the LOAD slot reads rows 0-3 (and the five W fragments), rows 4-7 are
+// read DURING the MFMA slot into the registers of rows 0-3 as soon as those have issued their MFMAs.  A granule is
+// therefore still read in its MFMA slot, so its ring slot (g % PP_RING) may only be refilled one granule later than
+// without the late reads: the DMA runs PP_RING-2 granules ahead, not PP_RING-1.  Every wave ends its LOAD slot with a
+// COUNTED vmcnt (one granule stays in flight) and every slot ends with a raw s_barrier, so a granule is only read after
 // the wait + barrier that retire it (cdna_hip_programming.md §5 "Read a staged buffer one phase AFTER the wait").
 // 8 waves x <=256 VGPRs leave room for the load-free epilogue (store_wave_tile), which the 16-wave tiles lack.
-//
-// ABL (ablation / instrumentation builds, reachable through ink_gemm_set_variant only): 1 no MFMA, 2 no LDS
-// reads / barriers, 4 every tile reads tile (0,0) (all L2 hits), 8 every workgroup writes (HW_ID, XCC_ID,
-// t_entry, t_filled, t_loop_end, t_stores_issued) in 100 MHz ticks through p.residual (tools/gemm_stamps.py).
-// TN = 4: 256x256 tile, TN = 5: 256x320 (wave tile 128 x 16*TN; 160 accumulator VGPRs).  LATE_A keeps only four of
-// the eight A fragments live: rows 4-7 are read DURING the MFMA slot into the registers of rows 0-3 as soon as
-// those have issued their MFMAs.  A granule is then still being read one slot later, so its ring slot may only be
-// refilled one granule later: the DMA runs RING-2 granules ahead instead of RING-1.
 // EPI: 0 = the epilogue is chosen at run time among the ABI-3 forms (bias / activation / layer scale / f32 residual,
 // f32 or f16 C); 1, 2, 3 = ONE compiled epilogue each for the SAM ViT-H block on the split-f16 residual stream:
 // 1 = folded LayerNorm -> f16 (qkv), 2 = folded LayerNorm + GELU -> f16 (lin1), 3 = split residual in, split C + row
 // statistics out (proj, lin2).  Separate kernels rather than more branches: with every form inside one kernel the
 // register allocator spilled around the dispatch.
-// EPI == 4 of the ping-pong kernel: an asm global load with a scalar base and a 32-bit lane offset (asm: hipcc turns
-// its own vmcnt waits into vmcnt(0) while an LDS-DMA is in flight; the loop's counted waits cover this load, see there)
-__device__ __forceinline__ void rmf_global_load(f32x4& dst, const float* base, uint32_t byte_off) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(byte_off), "s"(base) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_pp(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_pp<I + 1, N>(f);
-  }
-}
-
-template <int RING, int TN, int ABL = 0, bool LATE_A = (TN > 4), int EPI = 0>
+constexpr int PP_RING = 4, PP_TN = 5;
+template <int EPI>
 __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
+  constexpr int RING = PP_RING, TN = PP_TN;
   constexpr int BM = 256, BN = 64 * TN, BK = 32, NT = 512;
   constexpr int CPR = BK / 8, ROWB = BK * 2;
-  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB, GRAN = TILE_A + TILE_W;   // 32 KiB
+  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB, GRAN = TILE_A + TILE_W;   // 36 KiB
   constexpr int IT_A = (BM * CPR) / NT, IT_W = (BN * CPR) / NT;                    // 2 + 2 DMA per thread
   constexpr bool W_TAIL = (BN * CPR) % NT != 0;       // 320 rows: a third, half-populated round (waves 0-3 = group 0)
   static_assert(!W_TAIL || (BN * CPR) % NT == NT / 2, "tail is exactly the first four waves");
   constexpr int LOADS = IT_A + IT_W;                  // per wave of group 1; group 0 issues one more with W_TAIL
   constexpr int TM = 8, WNC = 16 * TN;
-  constexpr int AHEAD = LATE_A ? RING - 2 : RING - 1;   // granules the DMA runs ahead of the LOAD slot
-  constexpr int AG = LATE_A ? 4 : TM;                   // A fragments live at a time
-  static_assert(AHEAD >= 1, "ring too small");
+  constexpr int AHEAD = RING - 2;                     // granules the DMA runs ahead of the LOAD slot
+  constexpr int AG = 4;                               // A fragments live at a time
   constexpr int EP = WNC * 4 + 16;
   static_assert(8 * 16 * EP <= RING * GRAN, "patch fits");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2, wn = wave & 3;         // grp = wave row (128 rows each), wn = wave column (64 cols)
+  const int grp = wave >> 2, wn = wave & 3;         // grp = wave row (128 rows each), wn = wave column (80 cols)
   const int fr = lane & 15, fq = lane >> 4;
 
-  unsigned wg_rt[4] = {0, 0, 0, 0}, wg_cy[4] = {0, 0, 0, 0};
-  auto stamp_rt = [&](int k) {
-    if ((ABL & 8) && wave == 0) {
-      wg_rt[k] = (unsigned)__builtin_amdgcn_s_memrealtime();
-      wg_cy[k] = (unsigned)__builtin_readcyclecounter();
-    }
-  };
-  stamp_rt(0);
-  const float* dbg_out = EPI ? p.col_scale : p.residual;        // (stamp builds: the timeline leaves through a spare pointer)
-  if (ABL & 8) {
-    if (EPI) p.col_scale = nullptr; else p.residual = nullptr;
-  }
-
   const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM;
-  const int id = xcd_remap(blockIdx.x, ntm * ntn);
   int mt, nt;
-  const int gm_abs = group_m < 0 ? -group_m : group_m;
-  if (gm_abs > 1) {
-    const int per = gm_abs * ntn;
-    const int first = (id / per) * gm_abs;
-    const int gsz = min(ntm - first, gm_abs);
-    mt = first + (id % per) % gsz;
-    nt = (id % per) / gsz;
-  } else {
-    mt = id / ntn;
-    nt = id % ntn;
-  }
+  tile_of(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, group_m, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
-  const int sm0 = (ABL & 4) ? 0 : m0, sn0 = (ABL & 4) ? 0 : n0;
   const int G = p.K / BK;
   const f16* __restrict__ A = (const f16*)p.A;
   const f16* __restrict__ W = (const f16*)p.W;
@@ -585,12 +510,12 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
 #pragma unroll
   for (int it = 0; it < IT_A; ++it) {
     const int pch = it * NT + tid, row = pch / CPR, lch = (pch % CPR) ^ Swz<BK>::f(row);
-    srcA[it] = A + (size_t)min(sm0 + row, p.M - 1) * p.lda + lch * 8;
+    srcA[it] = A + (size_t)min(m0 + row, p.M - 1) * p.lda + lch * 8;
   }
 #pragma unroll
   for (int it = 0; it < IT_W + (W_TAIL ? 1 : 0); ++it) {
     const int pch = it * NT + tid, row = min(pch / CPR, BN - 1), lch = (pch % CPR) ^ Swz<BK>::f(row);
-    srcW[it] = W + (size_t)min(sn0 + row, p.N - 1) * p.ldw + lch * 8;
+    srcW[it] = W + (size_t)min(n0 + row, p.N - 1) * p.ldw + lch * 8;
   }
   auto dma = [&](int g, int slot) {
     char* base = smem + slot * GRAN;
@@ -603,25 +528,23 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
     if (W_TAIL && grp == 0)
       __builtin_amdgcn_global_load_lds((gptr_t)(srcW[IT_W] + g * BK), (lptr_t)(base + TILE_A + (IT_W * NT + wave * 64) * 16), 16, 0, 0);
   };
-  // counted wait that leaves the `ahead` most recent granules of THIS wave in flight
-  auto wait_ahead = [&](auto ahead_c) {
-    constexpr int ahead = decltype(ahead_c)::value;
+  // counted wait that leaves the AHEAD - 1 most recent granules of THIS wave in flight
+  auto wait_ahead = [&]() {
     if (W_TAIL && grp == 0) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ahead * (LOADS + 1)) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * (LOADS + 1)) : "memory");
     } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ahead * LOADS) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * LOADS) : "memory");
     }
   };
   auto slot_end = [&]() {
-    if (ABL & 2) return;
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // prologue: residual row indices, then RING-1 granules in flight (the launcher guarantees G >= RING-1), then
-  // the residual preload behind them; with a preload everything is drained once (the counted waits of the loop
-  // assume only DMA in flight), without one only granule 0 is waited for
+  // prologue: residual row indices, then AHEAD granules in flight (the launcher guarantees G >= PP_RING), then the
+  // residual preload behind them; with a preload everything is drained once (the counted waits of the loop assume
+  // only DMA in flight), without one only granule 0 is waited for
   int rows[TM];
   wave_rows<TM>(rows, p, m0 + grp * 128, lane);
   float2* strip = (float2*)(smem + RING * GRAN) + wave * (128 + WNC);   // behind the ring: rows + columns of the fold
@@ -629,44 +552,32 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
   for (int g = 0; g < AHEAD; ++g) dma(g, g);
   if (EPI == 1 || EPI == 2) ln_rows_prologue<TM, TN>(p, strip, m0 + grp * 128, n0 + wn * WNC, lane);   // (drains the fill, like a preload)
   f32x4 acc[TM][TN];
-  if constexpr (EPI == 4) {
-    // the f32 residual enters THROUGH THE MFMA PIPE during the K loop (below) instead of being preloaded into the
-    // accumulators: nothing to wait for here but granule 0
-#pragma unroll
-    for (int ti = 0; ti < TM; ++ti)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[ti][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    wait_ahead(std::integral_constant<int, AHEAD - 1>{});
+  init_wave_tile<TM, TN, EPI == 3>(acc, p, rows, n0 + wn * WNC, lane);
+  if (residual_preloaded(p) || EPI == 1 || EPI == 2) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
-    init_wave_tile<TM, TN, EPI == 3>(acc, p, rows, n0 + wn * WNC, lane);
-    if (residual_preloaded(p) || EPI == 1 || EPI == 2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      wait_ahead(std::integral_constant<int, AHEAD - 1>{});
-    }
+    wait_ahead();
   }
   slot_end();
   if (grp == 1) slot_end();                         // the stagger: group 1 idles through slot 0
-  stamp_rt(1);
 
   const int offA = (grp * 128 + fr) * ROWB;
   const int offW = (wn * WNC + fr) * ROWB;
   const int co = (fq ^ Swz<BK>::f(fr)) << 4;        // one k-step of 32 per granule: logical chunk = fq
   f16x8 a[AG], w[TN];
   int cslot = 0, islot = AHEAD % RING;
+  // one granule (a lambda, not a plain loop body: written as one, hipcc allocates the accumulators differently)
   auto iter = [&](int g) __attribute__((always_inline)) {
     const char* bA = smem + cslot * GRAN;
     const char* bW = bA + TILE_A;
     // ---- LOAD slot
-    if (!(ABL & 2) || g == 0) {
 #pragma unroll
-      for (int i = 0; i < AG; ++i) a[i] = *(const f16x8*)(bA + offA + i * 16 * ROWB + co);
+    for (int i = 0; i < AG; ++i) a[i] = *(const f16x8*)(bA + offA + i * 16 * ROWB + co);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) w[j] = *(const f16x8*)(bW + offW + j * 16 * ROWB + co);
-    }
+    for (int j = 0; j < TN; ++j) w[j] = *(const f16x8*)(bW + offW + j * 16 * ROWB + co);
     if (g + AHEAD < G) {
       dma(g + AHEAD, islot);
-      wait_ahead(std::integral_constant<int, AHEAD - 1>{});   // granule g+1 of this wave landed
+      wait_ahead();                                 // granule g+1 of this wave landed
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -675,109 +586,36 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    if (!(ABL & 1)) {
 #pragma unroll
-      for (int i0 = 0; i0 < TM; i0 += AG) {
+    for (int i0 = 0; i0 < TM; i0 += AG) {
 #pragma unroll
-        for (int i = 0; i < AG; ++i) {
+      for (int i = 0; i < AG; ++i) {
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[j], a[i], acc[i0 + i][j], 0, 0, 0);
-          if (LATE_A && i0 + AG < TM) {     // this fragment register is free: fetch the row AG further down
-            a[i] = *(const f16x8*)(bA + offA + (i0 + AG + i) * 16 * ROWB + co);
-            __builtin_amdgcn_sched_barrier(0);
-          }
+        for (int j = 0; j < TN; ++j)
+          acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[j], a[i], acc[i0 + i][j], 0, 0, 0);
+        if (i0 + AG < TM) {                         // this fragment register is free: fetch the row AG further down
+          a[i] = *(const f16x8*)(bA + offA + (i0 + AG + i) * 16 * ROWB + co);
+          __builtin_amdgcn_sched_barrier(0);
         }
       }
-    } else {
-#pragma unroll
-      for (int i = 0; i < AG; ++i) acc[i][0][0] += (float)a[i][0] + (float)w[i % TN][1];
     }
     __builtin_amdgcn_s_setprio(0);
-  };
-  auto iter_end = [&]() __attribute__((always_inline)) {
     slot_end();
     cslot = (cslot + 1 == RING) ? 0 : cslot + 1;
     islot = (islot + 1 == RING) ? 0 : islot + 1;
   };
-  if constexpr (EPI != 4) {
-    for (int g = 0; g < G; ++g) {
-      iter(g);
-      iter_end();
-    }
-  } else {
-    // ---- residual through the MFMA pipe.  The 40 accumulator tiles (ti, j) of the wave take their residual block
-    // R[16 rows, 16 columns] as  acc += I16 . hi(R)^T + I16 . lo(R)^T  (two v_mfma_f32_16x16x16_f16 with a 16 x 16
-    // identity as the first operand; hi = f16(R), lo = f16(R - hi): R to 2^-22), one tile every G / 40 granules.  The
-    // lane's f32x4 of R (the address the preload read) is fetched one step earlier by an asm global load issued in
-    // the MFMA slot, i.e. AFTER that granule's LDS-DMA: it is older than the next granule's DMA pieces, so the loop's
-    // counted vmcnt waits - unchanged - also cover it.  (With the preload all 256 workgroups of a round read their
-    // 328-KB residual tiles at once, before any MFMA: 17 us per round, 34 of proj's 135-146 us.)  The K loop is split
-    // into TM static blocks so that the accumulator row ti is a compile-time index and only j is a 5-way branch.
-    typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-    f32x4 rraw = {0.f, 0.f, 0.f, 0.f};
-    f16x4v idv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) idv[e] = (fr == 4 * fq + e) ? (f16)1.0f : (f16)0.0f;
-    const int gpb = G / TM, rstride = gpb / TN;          // granules per block / per residual step
-    const uint32_t roff0 = (uint32_t)(n0 + wn * WNC + fq * 4) * 4u;
-    auto rmf_apply = [&](auto tti, auto jj) __attribute__((always_inline)) {
-      constexpr int ti = decltype(tti)::value, j = decltype(jj)::value;
-      f16x4v hi, lo;
-      asm volatile("" : "+v"(rraw));       // (stays behind the loop's vmcnt waits, like every volatile asm)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (f16)rraw[e];
-        lo[e] = (f16)(rraw[e] - (float)hi[e]);
-      }
-      if (rows[ti] < 0) { hi = (f16x4v){0, 0, 0, 0}; lo = hi; }
-      acc[ti][j] = __builtin_amdgcn_mfma_f32_16x16x16f16(idv, hi, acc[ti][j], 0, 0, 0);
-      acc[ti][j] = __builtin_amdgcn_mfma_f32_16x16x16f16(idv, lo, acc[ti][j], 0, 0, 0);
-    };
-    auto rmf_load = [&](auto tti, int j) __attribute__((always_inline)) {
-      constexpr int ti = decltype(tti)::value;
-      rmf_global_load(rraw, p.residual, (uint32_t)max(rows[ti], 0) * (uint32_t)p.ldr * 4u + roff0 + (uint32_t)j * 64u);
-    };
-    static_for_pp<0, TM>([&](auto tti) {
-      constexpr int ti = decltype(tti)::value;
-      for (int gi = 0; gi < gpb; ++gi) {
-        iter(ti * gpb + gi);
-        if (gi % rstride == 0) {
-          const int j = gi / rstride;          // 0 .. TN - 1: apply the block loaded one step ago, then load (ti, j)
-          if (j == 0) {
-            if constexpr (ti > 0) rmf_apply(std::integral_constant<int, (ti > 0 ? ti - 1 : 0)>{}, std::integral_constant<int, TN - 1>{});
-          } else if (j == 1) {
-            rmf_apply(tti, std::integral_constant<int, 0>{});
-          } else if (j == 2) {
-            rmf_apply(tti, std::integral_constant<int, 1>{});
-          } else if (j == 3) {
-            rmf_apply(tti, std::integral_constant<int, 2>{});
-          } else {
-            rmf_apply(tti, std::integral_constant<int, (TN > 4 ? 3 : 0)>{});
-          }
-          rmf_load(tti, j);
-        }
-        iter_end();
-      }
-    });
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the last residual block
-    rmf_apply(std::integral_constant<int, TM - 1>{}, std::integral_constant<int, TN - 1>{});
-  }
+  for (int g = 0; g < G; ++g) iter(g);
   if (grp == 0) slot_end();                         // group 0 idles through the last slot (same barrier count)
-  stamp_rt(2);
 
   // ---- epilogue: the drained ring is the patch space
   char* er = smem + wave * (16 * EP);
-  // (group_m < 0: A/B switch of tools/gemm_res_ab.py - take the run-time-dispatch epilogue everywhere)
-  const bool plain = group_m > 0 && !p.col_scale && !(p.residual && !residual_preloaded(p));
+  const bool plain = !p.col_scale && !(p.residual && !residual_preloaded(p));
   if constexpr (EPI == 1) {
     store_wave_tile<TM, TN, 1, INK_ACT_NONE, true>(acc, p, er, rows, n0 + wn * WNC, lane, strip);
   } else if constexpr (EPI == 2) {
     store_wave_tile<TM, TN, 1, INK_ACT_GELU, true>(acc, p, er, rows, n0 + wn * WNC, lane, strip);
   } else if constexpr (EPI == 3) {
     store_wave_tile<TM, TN, 2, INK_ACT_NONE>(acc, p, er, rows, n0 + wn * WNC, lane);
-  } else if constexpr (EPI == 4) {
-    store_wave_tile<TM, TN, 0, INK_ACT_NONE>(acc, p, er, rows, n0 + wn * WNC, lane);
   } else if (p.c_f16) {
     if (plain && p.act == INK_ACT_GELU) {          // lin1 of the ViT-H MLP
       store_wave_tile<TM, TN, 1, INK_ACT_GELU>(acc, p, er, rows, n0 + wn * WNC, lane);
@@ -793,288 +631,43 @@ __global__ __launch_bounds__(512) void gemm_f16_nt_pp(InkGemm p, int group_m) {
       store_wave_tile<TM, TN, 0>(acc, p, er, rows, n0 + wn * WNC, lane);
     }
   }
-  if (ABL & 8) {
-    stamp_rt(3);                                    // stores issued (not retired)
-    if (wave == 0 && lane == 0) {
-      unsigned* out = (unsigned*)dbg_out + (size_t)blockIdx.x * 8;
-      out[0] = __builtin_amdgcn_s_getreg(63492);    // HW_ID
-      out[1] = __builtin_amdgcn_s_getreg(6164);     // XCC_ID
-      out[2] = wg_rt[0]; out[3] = wg_rt[1]; out[4] = wg_rt[2]; out[5] = wg_rt[3];
-      out[6] = wg_cy[2] - wg_cy[1];                 // shader cycles of the main loop
-      out[7] = wg_cy[3] - wg_cy[2];                 // ... of the epilogue
-    }
-  }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Persistent form of the 256x320 ping-pong kernel (ring of 4, LATE_A) for the three plain epilogues of the ViT-H
-// block: FORM 0 = f16 C (qkv), 1 = GELU -> f16 C (lin1), 2 = f32 C with an optional preloaded f32 residual (proj, lin2).
-// One workgroup per CU walks tiles b, b + grid, b + 2 grid, ... (the order the hardware dispatches the one-tile
-// kernel's workgroups in, so xcd_remap keeps its meaning).  The K loop of a tile is the one-tile kernel's.  What changes
-// is the tile boundary: a K = 1280 tile of the one-tile kernel is 2.2-3.9 us of pipeline fill + 37 us of loop + 4.6-7.4 us
-// of epilogue + ~1 us until the next workgroup starts on the CU, and the fill cannot start before the previous
-// workgroup's stores have retired.  Here the first two granules of tile t+1 are requested BEFORE the stores of tile t
-// are issued (the bias loads come first and are waited for, so that no load of the epilogue sits behind the DMA), and
-// one vmcnt(0) at the top of tile t+1 retires stores, fill and residual preload together.  The ring simply continues
-// (granule g of the next tile goes to the slot after the last one); the epilogue's patches live in the two slots the
-// fill does not use (every wave has left the K loop when the fill is issued: the groups' barrier counts are equal).
-// The earlier persistent attempt (round 1) kept the COUNTED waits running across tiles and over-waited on the stores.
-template <int TN, int FORM>
-__global__ __launch_bounds__(512) void gemm_f16_nt_pp_persist(InkGemm p, int group_m) {
-  constexpr int RING = 4, BM = 256, BN = 64 * TN, BK = 32, NT = 512;
-  constexpr int CPR = BK / 8, ROWB = BK * 2;
-  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB, GRAN = TILE_A + TILE_W;
-  constexpr int IT_A = (BM * CPR) / NT, IT_W = (BN * CPR) / NT;
-  constexpr bool W_TAIL = (BN * CPR) % NT != 0;
-  static_assert(!W_TAIL || (BN * CPR) % NT == NT / 2, "tail is exactly the first four waves");
-  constexpr int LOADS = IT_A + IT_W;
-  constexpr int TM = 8, WNC = 16 * TN, AHEAD = RING - 2, AG = 4;
-  constexpr int EP = WNC * 4 + 16;
-  static_assert(4 * 16 * EP <= GRAN, "the patches of four waves fit in one ring slot");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2, wn = wave & 3;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  const int ntn = p.N / BN, ntm = (p.M + BM - 1) / BM, ntiles = ntm * ntn;      // (launcher: N % BN == 0)
-  const int G = p.K / BK;
-  const f16* __restrict__ A = (const f16*)p.A;
-  const f16* __restrict__ W = (const f16*)p.W;
-  // DMA source rows: pointers formed as scalar base + 32-bit byte offset (the launcher checks that both operands are
-  // below 4 GiB) - with 64-bit index arithmetic hipcc keeps copies of the two bases in VGPRs across the K loop
-  const char* srcA[IT_A];
-  const char* srcW[IT_W + (W_TAIL ? 1 : 0)];
-  int m0, n0;
-  auto set_tile = [&](int v) {       // tile coordinates + DMA source rows of virtual workgroup v
-    const int id = xcd_remap(v, ntiles);
-    int mt, nt;
-    if (group_m > 1) {
-      const int per = group_m * ntn;
-      const int first = (id / per) * group_m;
-      const int gsz = min(ntm - first, group_m);
-      mt = first + (id % per) % gsz;
-      nt = (id % per) / gsz;
-    } else {
-      mt = id / ntn;
-      nt = id % ntn;
-    }
-    m0 = mt * BM;
-    n0 = nt * BN;
-#pragma unroll
-    for (int it = 0; it < IT_A; ++it) {
-      const int pch = it * NT + tid, row = pch / CPR, lch = (pch % CPR) ^ Swz<BK>::f(row);
-      srcA[it] = (const char*)A + ((uint32_t)min(m0 + row, p.M - 1) * (uint32_t)p.lda + (uint32_t)lch * 8u) * 2u;
-    }
-#pragma unroll
-    for (int it = 0; it < IT_W + (W_TAIL ? 1 : 0); ++it) {
-      const int pch = it * NT + tid, row = min(pch / CPR, BN - 1), lch = (pch % CPR) ^ Swz<BK>::f(row);
-      srcW[it] = (const char*)W + ((uint32_t)(n0 + row) * (uint32_t)p.ldw + (uint32_t)lch * 8u) * 2u;
-    }
-  };
-  auto dma = [&](int g, int slot) {
-    char* base = smem + slot * GRAN;
-#pragma unroll
-    for (int it = 0; it < IT_A; ++it)
-      __builtin_amdgcn_global_load_lds((gptr_t)(srcA[it] + g * (BK * 2)), (lptr_t)(base + (it * NT + wave * 64) * 16), 16, 0, 0);
-#pragma unroll
-    for (int it = 0; it < IT_W; ++it)
-      __builtin_amdgcn_global_load_lds((gptr_t)(srcW[it] + g * (BK * 2)), (lptr_t)(base + TILE_A + (it * NT + wave * 64) * 16), 16, 0, 0);
-    if (W_TAIL && grp == 0)
-      __builtin_amdgcn_global_load_lds((gptr_t)(srcW[IT_W] + g * (BK * 2)), (lptr_t)(base + TILE_A + (IT_W * NT + wave * 64) * 16), 16, 0, 0);
-  };
-  auto wait_one_granule = [&]() {      // leaves the most recent granule of THIS wave in flight (AHEAD - 1 = 1)
-    if (W_TAIL && grp == 0) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS + 1) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
-    }
-  };
-  auto slot_end = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  const int offA = (grp * 128 + fr) * ROWB;
-  const int offW = (wn * WNC + fr) * ROWB;
-  const int co = (fq ^ Swz<BK>::f(fr)) << 4;
-  int cslot = 0;                      // ring slot of the next granule to be consumed
-  int v = blockIdx.x;
-  set_tile(v);
-  // output rows of the wave tile at m0 (no row map here: the launcher sends those to the one-tile kernel); recomputed
-  // where they are needed instead of living across the K loop
-  auto tile_rows = [&](int (&rows)[TM], int mbase) {
-#pragma unroll
-    for (int ti = 0; ti < TM; ++ti) {
-      const int m = mbase + grp * 128 + ti * 16 + fr;
-      rows[ti] = m < p.M ? m : -1;
-    }
-  };
-#pragma unroll
-  for (int g = 0; g < AHEAD; ++g) dma(g, g);
-
-  for (;;) {
-    // ---- top of a tile: its first AHEAD granules are in flight (behind the previous tile's stores)
-    f32x4 acc[TM][TN];
-    if constexpr (FORM == 2) {
-      int rows[TM];
-      tile_rows(rows, m0);
-      init_wave_tile<TM, TN>(acc, p, rows, n0 + wn * WNC, lane);
-    } else {
-#pragma unroll
-      for (int ti = 0; ti < TM; ++ti)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[ti][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    slot_end();
-    if (grp == 1) slot_end();                       // the stagger: group 1 idles through slot 0
-    f16x8 a[AG], w[TN];
-    int islot = (cslot + AHEAD) & (RING - 1);
-    for (int g = 0; g < G; ++g) {
-      const char* bA = smem + cslot * GRAN;
-      const char* bW = bA + TILE_A;
-      // ---- LOAD slot
-#pragma unroll
-      for (int i = 0; i < AG; ++i) a[i] = *(const f16x8*)(bA + offA + i * 16 * ROWB + co);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) w[j] = *(const f16x8*)(bW + offW + j * 16 * ROWB + co);
-      if (g + AHEAD < G) {
-        dma(g + AHEAD, islot);
-        wait_one_granule();
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      slot_end();
-      // ---- MFMA slot
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i0 = 0; i0 < TM; i0 += AG) {
-#pragma unroll
-        for (int i = 0; i < AG; ++i) {
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[j], a[i], acc[i0 + i][j], 0, 0, 0);
-          if (i0 + AG < TM) {
-            a[i] = *(const f16x8*)(bA + offA + (i0 + AG + i) * 16 * ROWB + co);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-      slot_end();
-      cslot = (cslot + 1) & (RING - 1);
-      islot = (islot + 1) & (RING - 1);
-    }
-    if (grp == 0) slot_end();                       // group 0 idles through the last slot (same barrier count)
-
-    // ---- tile boundary.  Every wave has issued its last ring read (group 1's LATE_A reads precede the barrier
-    // group 0 has just passed).  Bias first: the epilogue's only loads.  The empty asm USES the loaded registers, so the
-    // compiler's wait for them sits here, in front of the DMA (behind it, it would be a vmcnt(0) that waits for the fill)
-    f32x4 bv[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (p.bias) bv[j] = *(const f32x4*)(p.bias + n0 + wn * WNC + j * 16 + fq * 4);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bv[j]) : : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    // ... then the next tile's fill into slots cslot, cslot + 1 ...
-    const int n0_cur = n0, m0_cur = m0;
-    v += gridDim.x;
-    const bool more = v < ntiles;
-    if (more) {
-      set_tile(v);
-      __builtin_amdgcn_sched_barrier(0);            // (all address arithmetic in front of the first DMA piece)
-#pragma unroll
-      for (int g = 0; g < AHEAD; ++g) dma(g, (cslot + g) & (RING - 1));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // ... then the stores, patches in slots cslot + 2 (group 0) and cslot + 3 (group 1)
-#pragma unroll
-    for (int ti = 0; ti < TM; ++ti)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[ti][j] += bv[j];
-    int rows[TM];
-    tile_rows(rows, m0_cur);
-    char* er = smem + ((cslot + 2 + grp) & (RING - 1)) * GRAN + wn * (16 * EP);
-    if constexpr (FORM == 0) {
-      store_wave_tile<TM, TN, 1, INK_ACT_NONE, false, false>(acc, p, er, rows, n0_cur + wn * WNC, lane);
-    } else if constexpr (FORM == 1) {
-      store_wave_tile<TM, TN, 1, INK_ACT_GELU, false, false>(acc, p, er, rows, n0_cur + wn * WNC, lane);
-    } else {
-      store_wave_tile<TM, TN, 0, INK_ACT_NONE, false, false>(acc, p, er, rows, n0_cur + wn * WNC, lane);
-    }
-    if (!more) break;
-  }
-}
-
-template <int TN, int FORM>
-static int launch_gemm_pp_persist(const InkGemm& p, hipStream_t s, int group_m) {
-  constexpr int BN = 64 * TN;
-  constexpr int lds = 4 * (256 + BN) * 32 * 2;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  if (p.K / 32 < 4 || p.N % BN != 0 || p.ln_stats || p.c_f16 == 2 || p.res_hi || p.col_scale || p.row_map) return INK_ERR_ARG;
-  if (p.residual && p.act != INK_ACT_NONE) return INK_ERR_ARG;      // (a late residual: the one-tile kernel)
-  if ((int64_t)p.M * p.lda * 2 >= ((int64_t)1 << 32) || (int64_t)p.N * p.ldw * 2 >= ((int64_t)1 << 32)) return INK_ERR_ARG;
-  static int n_cu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipFuncSetAttribute((const void*)gemm_f16_nt_pp_persist<TN, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return n > 0 ? n : 256;
-  }();
-  const int ntiles = ((p.M + 255) / 256) * (p.N / BN);
-  hipLaunchKernelGGL((gemm_f16_nt_pp_persist<TN, FORM>), dim3(ntiles < n_cu ? ntiles : n_cu), dim3(512), lds, s, p, group_m);
-  return ink_launch_status();
-}
-
-template <int RING, int TN = 4, int ABL = 0, bool LATE_A = (TN > 4), int EPI = 0>
+template <int EPI>
 static int launch_gemm_pp(const InkGemm& p, hipStream_t s, int group_m) {
-  if (p.K / 32 < RING) return 1;
+  if (p.K / 32 < PP_RING) return INK_ERR_ARG;
   if (EPI == 0 && (p.ln_stats || p.c_f16 == 2 || p.res_hi)) return INK_ERR_ARG;
-  if (EPI == 4 && !(TN == 5 && p.residual && !p.c_f16 && p.act == INK_ACT_NONE && !p.col_scale && (p.K / 32) % 40 == 0 &&
-                    (int64_t)p.M * p.ldr * 4 < ((int64_t)1 << 32))) return INK_ERR_ARG;
-  constexpr int BN = 64 * TN;
-  constexpr int lds = RING * (256 + BN) * 32 * 2 + 8 * (128 + 16 * TN) * 8;   // ring + the LayerNorm-fold strips of the 8 waves
+  constexpr int BN = 64 * PP_TN;
+  constexpr int lds = PP_RING * (256 + BN) * 32 * 2 + 8 * (128 + 16 * PP_TN) * 8;   // ring + the LayerNorm-fold strips of the 8 waves
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt_pp<RING, TN, ABL, LATE_A, EPI>,
+  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt_pp<EPI>,
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)attr;
   const int ntiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_f16_nt_pp<RING, TN, ABL, LATE_A, EPI>), dim3(ntiles), dim3(512), lds, s, p, group_m);
+  hipLaunchKernelGGL((gemm_f16_nt_pp<EPI>), dim3(ntiles), dim3(512), lds, s, p, group_m);
   return ink_launch_status();
 }
 
-template <int BM, int BN, int BK, int WM, int WN, int NS, int ABL = 0, bool EXT = false>
+template <int BM, int BN, int BK, int WM, int WN, bool EXT>
 static int launch_gemm(const InkGemm& p, hipStream_t s, int group_m = 1) {
   constexpr int lds = NS * (BM + BN) * BK * 2 + (EXT ? (BM * WN + BN * WM) * 8 : 0);   // staging (+ the LayerNorm-fold strips)
   static_assert(lds <= 160 * 1024, "LDS budget");
   if (!EXT && (p.ln_stats || p.c_f16 == 2 || p.res_hi)) return INK_ERR_ARG;
-  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt<BM, BN, BK, WM, WN, NS, ABL, EXT>,
+  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt<BM, BN, BK, WM, WN, EXT>,
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)attr;
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_f16_nt<BM, BN, BK, WM, WN, NS, ABL, EXT>), dim3(ntm * ntn), dim3(WM * WN * 64), lds, s, p, group_m);
+  hipLaunchKernelGGL((gemm_f16_nt<BM, BN, BK, WM, WN, EXT>), dim3(ntm * ntn), dim3(WM * WN * 64), lds, s, p, group_m);
   return ink_launch_status();
 }
 
 }  // namespace
 
-static int g_variant = -1;
-// variant 55 (persistent workgroups) for the f16-output projections: 3-4 % faster per launch and 0.6 ms per encoder pass,
-// but the overlapped step is 1.2 ms SLOWER with it - a persistent grid holds every CU for the whole launch, and the
-// detector stream's kernels can no longer slip onto CUs between tiles (tools/stage_times.py A/B, profiles/r03_gemm_persist_ab.txt)
-constexpr bool PERSIST_DEFAULT = false;
-constexpr bool RMF_DEFAULT = false;   // variant 54 (residual through the MFMA pipe) for the eligible in-place f32 projections
-// shape heuristic (tools/gemm_sweep.py on MI355X): the ping-pong 256x320 tile when N is a multiple of 320 and the
-// launch is at least ~1.5 rounds of 256 CUs (SAM ViT-H: N = 1280 / 3840 / 5120, where batch 8 gives exact round
-// counts and 10 % fewer staged bytes per flop than 256x256); else the 16-wave 256x256 tile whenever it fills the
-// chip (>= ~200 tiles) and N does not waste a large part of a 256-wide tile; else the 128x128 tile.
+static int g_variant = -1;   // ink_gemm_set_variant: -1 = the shape heuristic, else the forced tile family
+// shape heuristic (tile sweeps on MI355X): the ping-pong 256x320 tile when N is a multiple of 320 and
+// the launch is at least ~1.5 rounds of 256 CUs (SAM ViT-H: N = 1280 / 3840 / 5120, where batch 8 gives
+// exact round counts and 10 % fewer staged bytes per flop than 256x256); else the 16-wave 256x256 tile whenever it
+// fills the chip (>= ~200 tiles) and N does not waste a large part of a 256-wide tile; else the 128x128 tile.
 extern "C" int ink_gemm_query_variant(int32_t M, int32_t N, int32_t K) {
   if (K % 64 != 0) return 32;      // 128x128x32 tile
   if (N % 320 == 0 && K >= 128 && (long)((M + 255) / 256) * (N / 320) >= 384) return 45;
@@ -1089,18 +682,8 @@ extern "C" int ink_gemm_query_stats_chunk(int32_t M, int32_t N, int32_t K) {
 }
 extern "C" int ink_abi_version(void) { return INK_ABI_VERSION; }
 extern "C" int ink_gemm_set_variant(int32_t v) {
-  // A process-wide override for the sweep / debugging tools (not thread-safe, not used by the product path).
-  // v = gm * 100 + variant; + 10000: the ping-pong kernel takes its run-time-dispatch epilogue (A/B of the
-  // compile-time activation modes, tools/gemm_res_ab.py)
-  const int vv = v >= 10000 ? v - 10000 : v;
-  const int base = vv >= 100 ? vv % 100 : vv;
-  bool ok = v == -2 || base == -1 || base == 0 || base == 10 || base == 11 || base == 12 || base == 14 || base == 16 ||
-            base == 32 || base == 40 || base == 42 || base == 45 || base == 47 || base == 53 || base == 54 || base == 55;
-#ifdef INK_ABLATION
-  ok = ok || (base >= 21 && base <= 23) || base == 43 || base == 44 || base == 46 || (base >= 48 && base <= 52) ||
-       (base >= 61 && base <= 63);
-#endif
-  INK_CHECK_ARG(ok);
+  // test hook (process-wide, not thread-safe, not used by the product path): force one tile family of the heuristic
+  INK_CHECK_ARG(v == -1 || v == 0 || v == 10 || v == 45);
   g_variant = v;
   return INK_OK;
 }
@@ -1118,94 +701,38 @@ extern "C" int ink_gemm_f16(const InkGemm* pp, void* stream) {
   INK_CHECK_ARG(((uintptr_t)p.C & 15) == 0);
   INK_CHECK_ARG(p.act >= 0 && p.act <= 2);
   INK_CHECK_ARG(p.c_f16 >= 0 && p.c_f16 <= 2 && (p.c_f16 != 2 || (p.C_lo && ((uintptr_t)p.C_lo & 15) == 0)));
-#ifndef INK_ABLATION      // (the stamp builds pass their debug buffer through col_scale)
   INK_CHECK_ARG(!p.res_hi || !p.col_scale);
-#endif
   INK_CHECK_ARG(!p.res_hi || (p.res_lo && !p.residual && p.ldr % 4 == 0 && p.ldr >= p.N && p.act == INK_ACT_NONE));
   INK_CHECK_ARG(!p.ln_stats || (p.ln_colsum && p.ln_parts > 0 && p.ln_parts <= 20 && p.ln_parts % 2 == 0 &&
                                 p.ln_dim > 0 && !p.row_map && ((uintptr_t)p.ln_stats & 15) == 0));
   hipStream_t s = (hipStream_t)stream;
-  int v = g_variant;           // -1 (default): shape heuristic.  No environment variable reaches this function.
-  const bool one_tile_only = v == -2;      // -2: the heuristic without the persistent form (A/B of whole steps)
-  if (one_tile_only) v = -1;
-  int gm = 1;
-  bool generic_epilogue = false;
-  if (v >= 10000) { generic_epilogue = true; v -= 10000; }
-  if (v >= 100) { gm = v / 100; v = v % 100; }
   const bool ext = p.ln_stats || p.c_f16 == 2 || p.res_hi;      // ABI-4 forms: ping-pong or 128x128 tiles only
-  if (p.K % 64 != 0) return launch_gemm<128, 128, 32, 2, 2, 2, 0, true>(p, s);
+  if (p.K % 64 != 0) return launch_gemm<128, 128, 32, 2, 2, true>(p, s);
+  int v = g_variant;           // -1 (default): shape heuristic.  No environment variable reaches this function.
   if (v < 0) {
     v = ink_gemm_query_variant(p.M, p.N, p.K);
-    gm = 4;
-    if (ext && v == 10) { v = 0; gm = 1; }
+    if (ext && v == 10) v = 0;
   }
   if (p.stats_out) {      // row statistics are per wave-tile chunk: the split output only, whole chunks only
-    const bool pp3 = (v == 45 && !p.ln_stats && !p.col_scale && !p.row_map && p.res_hi && p.act == INK_ACT_NONE) || v == 63;
+    const bool pp3 = v == 45 && !p.ln_stats && !p.col_scale && !p.row_map && p.res_hi && p.act == INK_ACT_NONE;
     const int chunk = pp3 ? 80 : 64;
-    INK_CHECK_ARG(p.c_f16 == 2 && p.N % chunk == 0 && p.stats_parts == p.N / chunk && (g_variant < 0 || v == 63));
+    INK_CHECK_ARG(p.c_f16 == 2 && p.N % chunk == 0 && p.stats_parts == p.N / chunk && g_variant < 0);
   }
-  // Production variants: 0 / 32 (128x128 tiles, K step 64 / 32), 10 (16-wave 256x256), 45 (ping-pong 256x320).
-  // 40/42/47/53/54/55/16/12/14/11 are alternative CORRECT tilings kept for tools/gemm_sweep.py (ink_gemm_set_variant).
-  // The ablation / instrumentation kernels DESIGN.md's measurements come from (they skip MFMAs, loads or the
-  // epilogue and return garbage) exist only in a library built with -DINK_ABLATION (`python -m inklayer_amd.build
-  // --ablation`, tools/gemm_stamps.py); the shipped library rejects their numbers in ink_gemm_set_variant.
-  const bool persist_ok = !ext && !generic_epilogue && !p.col_scale && !p.row_map && (int64_t)p.M * p.lda * 2 < ((int64_t)1 << 32) &&
-                          (int64_t)p.N * p.ldw * 2 < ((int64_t)1 << 32) && p.N % 320 == 0 && p.K >= 128 && p.act != INK_ACT_RELU &&
-                          (p.c_f16 == 1 ? !p.residual : (p.act == INK_ACT_NONE));
-  const bool rmf_ok = !ext && !generic_epilogue && p.residual && !p.c_f16 && p.act == INK_ACT_NONE && !p.col_scale &&
-                      !p.row_map && (p.K / 32) % 40 == 0 && (int64_t)p.M * p.ldr * 4 < ((int64_t)1 << 32);
+  // 0 / 32: 128x128 tiles (K step 64 / 32) in row-major tile order; 10, 45: the large tiles in groups of 4 M-tiles
   switch (v) {
-    case 10: return launch_gemm<256, 256, 64, 4, 4, 2>(p, s, gm);       // 16 waves x (64x64), 2 x 64 KB stages
-    case 45: {                                                          // ping-pong 256x320, ring of 4 (144 KB)
+    case 10: return launch_gemm<256, 256, 64, 4, 4, false>(p, s, 4);   // 16 waves x (64x64), 2 x 64 KB stages
+    case 45:                                                           // ping-pong 256x320, ring of 4 (144 KB)
       if (ext) {       // the ViT-H block forms on the split-f16 stream: one specialised kernel each
         const bool simple = !p.col_scale && !p.row_map;
         if (p.ln_stats && p.c_f16 == 1 && simple && !p.residual && !p.res_hi && p.act == INK_ACT_NONE)
-          return launch_gemm_pp<4, 5, 0, true, 1>(p, s, gm);
+          return launch_gemm_pp<1>(p, s, 4);
         if (p.ln_stats && p.c_f16 == 1 && simple && !p.residual && !p.res_hi && p.act == INK_ACT_GELU)
-          return launch_gemm_pp<4, 5, 0, true, 2>(p, s, gm);
+          return launch_gemm_pp<2>(p, s, 4);
         if (!p.ln_stats && p.c_f16 == 2 && simple && p.res_hi && p.act == INK_ACT_NONE)
-          return launch_gemm_pp<4, 5, 0, true, 3>(p, s, gm);
-        return launch_gemm<128, 128, 64, 2, 2, 2, 0, true>(p, s);      // any other combination: the general tile
+          return launch_gemm_pp<3>(p, s, 4);
+        return launch_gemm<128, 128, 64, 2, 2, true>(p, s);      // any other combination: the general tile
       }
-      // f16 C (qkv, lin1 of the ViT-H blocks): the persistent form is 3-4 % faster at K = 1280 (tools/gemm_persist_ab.py;
-      // with an f32 C + residual 1-2 % slower) - see PERSIST_DEFAULT for why it is not dispatched
-      if (PERSIST_DEFAULT && g_variant < 0 && !one_tile_only && persist_ok && p.c_f16 == 1)
-        return p.act == INK_ACT_GELU ? launch_gemm_pp_persist<5, 1>(p, s, gm) : launch_gemm_pp_persist<5, 0>(p, s, gm);
-      if (RMF_DEFAULT && g_variant < 0 && rmf_ok) return launch_gemm_pp<4, 5, 0, true, 4>(p, s, gm);
-      return launch_gemm_pp<4, 5>(p, s, generic_epilogue ? -gm : gm);
-    }
-    case 55: {                                                          // persistent 256x320 (plain epilogues only)
-      INK_CHECK_ARG(persist_ok);
-      if (p.c_f16) return p.act == INK_ACT_GELU ? launch_gemm_pp_persist<5, 1>(p, s, gm) : launch_gemm_pp_persist<5, 0>(p, s, gm);
-      return launch_gemm_pp_persist<5, 2>(p, s, gm);
-    }
-    case 54:                                                            // 256x320, f32 residual through the MFMA pipe
-      INK_CHECK_ARG(rmf_ok);
-      return launch_gemm_pp<4, 5, 0, true, 4>(p, s, gm);
-    case 40: return launch_gemm_pp<4>(p, s, gm);                        // ping-pong 256x256, ring of 4 (128 KB)
-    case 42: return launch_gemm_pp<3>(p, s, gm);                        // ... ring of 3 (96 KB)
-    case 47: return launch_gemm_pp<3, 5>(p, s, gm);                     // 256x320, ring of 3 (DMA 1 granule ahead)
-    case 53: return launch_gemm_pp<4, 5, 0, false>(p, s, gm);           // 256x320, 8 A fragments live, 3 ahead
-    case 16: return launch_gemm<128, 128, 64, 2, 2, 2>(p, s, gm);       // variant 0 with grouped tile order
-    case 12: return launch_gemm<128, 256, 64, 2, 4, 2>(p, s);           // 8 waves x (64x64), 96 KB
-    case 14: return launch_gemm<256, 128, 32, 4, 2, 2>(p, s, gm);       // 48 KB: 3 workgroups / CU
-    case 11: return launch_gemm<256, 256, 32, 4, 4, 4>(p, s);           // 16 waves, counted-vmcnt ring of 4 x K32
-#ifdef INK_ABLATION
-    case 21: return launch_gemm<256, 256, 64, 4, 4, 2, 1>(p, s, gm);    // variant 10 ablations: no DMA after tile 1
-    case 22: return launch_gemm<256, 256, 64, 4, 4, 2, 2>(p, s, gm);    // ... no MFMA
-    case 23: return launch_gemm<256, 256, 64, 4, 4, 2, 3>(p, s, gm);    // ... no epilogue
-    case 43: return launch_gemm_pp<4, 4, 1>(p, s, gm);                  // ping-pong ablations (see the kernel comment)
-    case 44: return launch_gemm_pp<4, 4, 3>(p, s, gm);
-    case 46: return launch_gemm_pp<4, 4, 7>(p, s, gm);
-    case 48: return launch_gemm_pp<4, 4, 8>(p, s, gm);                  // per-workgroup timeline, 256x256
-    case 49: return launch_gemm_pp<4, 5, 8>(p, s, gm);                  // ... 256x320
-    case 50: return launch_gemm_pp<4, 5, 9>(p, s, gm);                  // ... without MFMA
-    case 51: return launch_gemm_pp<4, 5, 11>(p, s, gm);                 // ... pure DMA stream
-    case 52: return launch_gemm_pp<4, 5, 15>(p, s, gm);                 // ... pure DMA stream, all L2 hits
-    case 61: return launch_gemm_pp<4, 5, 8, true, 1>(p, s, gm);         // per-workgroup timeline of the ABI-4 forms
-    case 62: return launch_gemm_pp<4, 5, 8, true, 2>(p, s, gm);         //   (stamps leave through col_scale)
-    case 63: return launch_gemm_pp<4, 5, 8, true, 3>(p, s, gm);
-#endif
-    default: return launch_gemm<128, 128, 64, 2, 2, 2, 0, true>(p, s);  // variant 0
+      return launch_gemm_pp<0>(p, s, 4);
+    default: return launch_gemm<128, 128, 64, 2, 2, true>(p, s);  // variant 0
   }
 }

@@ -46,18 +46,26 @@ def test_bad_arguments_are_rejected_without_launch():
     assert l.ink_add_split_f16(16, None, 0, 16, 8, 3, None) == 1            # C % 4 != 0
 
 
-def test_shipped_library_has_no_ablation_gemm_variants():
-    """VERDICT r1 / ADVICE: the no-MFMA / no-epilogue / timeline GEMM kernels return garbage fast and must not be
-    reachable in the product library (they live in the -DINK_ABLATION build used by tools/), and no environment
-    variable may select a GEMM variant."""
+def test_gemm_variant_hook_accepts_only_shipped_tile_families():
+    """VERDICT r1 / ADVICE: the library ships only the GEMM tile families the shape heuristic dispatches, and the test
+    hook ink_gemm_set_variant accepts exactly those (-1 = the heuristic): no sweep tiling, no persistent or
+    residual-through-MFMA form, no A/B encoding, no ablation kernel.  No environment variable may select a GEMM variant,
+    and no kernel source carries a compile-time experiment switch (no preprocessor conditional at all)."""
     from inklayer_amd import _lib
-    l = _lib.lib()
-    for v in (21, 22, 23, 43, 44, 46, 48, 49, 50, 51, 52, 7, 99):
-        assert l.ink_gemm_set_variant(v) == 1, v
-    for v in (0, 10, 45, 445, 454, 455, -2, -1):
-        assert l.ink_gemm_set_variant(v) == 0, v
+    lib = _lib.lib()
+    shipped = {-1, 0, 10, 45}
+    removed = (11, 12, 14, 16, 32, 40, 42, 47, 53, 54, 55, 445, 454, 455, -2, 10045)
+    ablation = (21, 22, 23, 43, 44, 46, 48, 49, 50, 51, 52, 61, 62, 63)
+    try:
+        for v in (*removed, *ablation, *range(-4, 1000), 10000, 10010, 10445):
+            assert lib.ink_gemm_set_variant(v) == (0 if v in shipped else 1), v
+    finally:
+        lib.ink_gemm_set_variant(-1)
     src = (ROOT / "inklayer_amd" / "csrc" / "gemm.hip").read_text()
     assert "getenv" not in src
+    for f in sorted((ROOT / "inklayer_amd" / "csrc").iterdir()):
+        cond = [ln for ln in f.read_text().splitlines() if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", ln)]
+        assert not cond, (f.name, cond)
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -10,7 +10,7 @@ v = int(sys.argv[4]) if len(sys.argv) > 4 else -1
 g = torch.Generator().manual_seed(1)
 a = (torch.randn(M, K, generator=g) * 0.5).half().to(dev); w = (torch.randn(N, K, generator=g) * 0.1).half().to(dev)
 bias = torch.randn(N, generator=g).to(dev)
-_lib.lib().ink_gemm_set_variant(v)
+assert _lib.lib().ink_gemm_set_variant(v) == 0, "variant: -1 (heuristic), 0, 10 or 45"
 for od in (torch.float32, torch.float16):
     out = ops.gemm(a, w, bias, out_dtype=od)
     ref = a.double() @ w.double().t() + bias.double()

@@ -10,7 +10,7 @@ dev = torch.device("cuda:0")
 a = torch.randn(m, k, device=dev).half(); w = (torch.randn(n, k, device=dev) * 0.05).half()
 bias = torch.randn(n, device=dev)
 out = torch.empty(m, n, device=dev, dtype=torch.float16)
-_lib.lib().ink_gemm_set_variant(variant)
+assert _lib.lib().ink_gemm_set_variant(variant) == 0, "variant: -1 (heuristic), 0, 10 or 45"
 for _ in range(5):
     ops.gemm(a, w, bias, out=out)
 torch.cuda.synchronize()
