@@ -482,6 +482,56 @@ int ink_mask_cleanup(const void* masks_u8, int32_t n, int32_t H, int32_t W, int3
 int ink_mask_sketch_iou_counts(const void* masks_u8, const void* sketch_rgb_u8, int32_t n, int32_t H, int32_t W,
                                void* bits_ws_u64, int32_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SamAutomaticMaskGenerator's tail on low-res logits (SA/automatic_mask_generator.py:266-321, SA/utils/amg.py).
+ * COLUMN-MAJOR BIT PLANES: Hp = ceil(H / 64) uint64 words per column, bit b of word w of column x = pixel (64 w + b, x),
+ * bits of rows >= H are 0; m planes are [m, W, Hp] - the order mask_to_rle_pytorch walks.  H, W <= 16383.
+ *
+ * ink_sam_amg_stats: for the masks index[0..m) of low f32 [n, S, S] (index NULL: masks 0..m; m_dev non-NULL: a device
+ * int32, workgroups of masks >= *m_dev do nothing, so a filter made on the device needs no host round trip), with
+ * v = Sam.postprocess_masks(low) resized to crop_h x crop_w - bit-identical to what ink_sam_postprocess writes to
+ * out_logits for the same sizes, and never stored unless out_logits (f32 [m, crop_h, crop_w], test hook) is given:
+ *   table int32 [m, 8] = count(v > thr + offset), count(v > thr - offset) (calculate_stability_score, amg.py:156-176),
+ *     count(v > thr), then x_min, y_min, x_max, y_max of v > thr in crop coordinates (batched_mask_to_box,
+ *     amg.py:303-346: inclusive maxima, 0 0 0 0 for an empty mask), 0;
+ *   planes uint64 [m, orig_w, ceil(orig_h / 64)] = v > thr placed at (x0, y0) of the orig_h x orig_w frame, zeros
+ *     outside the crop (uncrop_masks, amg.py:255-264).
+ * thr and offset are doubles because the reference's are Python floats: each cut-off (thr, thr + offset, thr - offset) is
+ * made in double and rounded to f32 once, as torch does for `tensor > python_float`.
+ * The table and, for a true crop, the planes are zeroed on the stream first. */
+int ink_sam_amg_stats(const float* low, int32_t n, const int32_t* index, int32_t m, const int32_t* m_dev, int32_t S,
+                      int32_t L, int32_t in_h, int32_t in_w, int32_t crop_h, int32_t crop_w, double thr, double offset,
+                      int32_t x0, int32_t y0, int32_t orig_h, int32_t orig_w, int32_t* table, void* planes_u64,
+                      float* out_logits, void* stream);
+
+/* mask_to_rle_pytorch (amg.py:107-135) for the planes select[0..k) (select NULL: planes 0..k) of H x W images:
+ * ink_mask_rle_counts writes the number of counts of each mask (n_counts int32 [k]); ink_mask_rle_write writes the counts
+ * themselves (column-major runs, the first one the leading zero run, hence 0 when the mask starts with a one) to
+ * counts + offsets[i] (offsets int32 [k] = the caller's exclusive scan of n_counts). */
+int ink_mask_rle_counts(const void* planes_u64, const int32_t* select, int32_t k, int32_t H, int32_t W,
+                        int32_t* n_counts, void* stream);
+int ink_mask_rle_write(const void* planes_u64, const int32_t* select, int32_t k, int32_t H, int32_t W,
+                       const int32_t* offsets, int32_t* counts, void* stream);
+
+/* remove_small_regions (amg.py:267-291) for k column-major planes of H x W images, one mode per call: holes != 0 fills the
+ * 8-connected components of the COMPLEMENT with area < min_area; holes == 0 removes the components of the mask with
+ * area < min_area, and if every one is that small keeps the largest (of equal areas the one whose first pixel comes first
+ * in raster order: cv2.connectedComponentsWithStats' label order).  changed int32 [k] = 1 where a component below
+ * min_area existed (the reference's flag), else 0.  tmp_planes: k planes of scratch; out_planes may be planes itself;
+ * workspace: int32[ink_mask_small_regions_workspace_ints(k, H, W)], sized for the true run bound ceil(H / 2) per column,
+ * so no mask can overflow it. */
+int ink_mask_small_regions_workspace_ints(int32_t k, int32_t H, int32_t W, int64_t* out_ints);
+int ink_mask_small_regions(const void* planes_u64, int32_t k, int32_t H, int32_t W, int32_t min_area, int32_t holes,
+                           void* tmp_planes_u64, int32_t* workspace, void* out_planes_u64, int32_t* changed, void* stream);
+
+/* torchvision.ops.nms for one category (batched_nms with idxs == 0, automatic_mask_generator.py:214-220, 251-257,
+ * 357-362): boxes f32 [n, 4] xyxy, area = (x2 - x1)(y2 - y1), iou = inter / (a_i + a_j - inter) in f32, a box is
+ * suppressed by a kept box of higher rank when iou > iou_threshold; rank = descending score, TIES TO THE LOWER INDEX
+ * (torchvision leaves the order of ties open).  Scores must not be NaN.  keep int32 [n] = the kept indices in rank
+ * order, *n_keep their number.  n <= 4096 (else return 1); workspace: uint64[n * (ceil(n / 64) + 3)], 16-byte aligned. */
+int ink_box_nms(const float* boxes, const float* scores, int32_t n, float iou_threshold, void* workspace_u64,
+                int32_t* keep, int32_t* n_keep, void* stream);
+
 /* The SAM ViT-H residual stream as two f16 planes (x = hi + lo, hi = f16(x), lo = f16(x - hi): ~22 significant bits),
  * so that the hi plane IS the f16 operand of the next projection and LayerNorm folds into that projection
  * (InkGemm.ln_stats; SA/modeling/image_encoder.py:166-182).

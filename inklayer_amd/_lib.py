@@ -69,6 +69,14 @@ SIGNATURES = {
                            c_void_p],
     "ink_sam_postprocess": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                             c_void_p, c_void_p, c_void_p],
+    "ink_sam_amg_stats": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double,
+                          C.c_double, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_mask_rle_counts": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_mask_rle_write": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_mask_small_regions_workspace_ints": [c_int, c_int, c_int, C.POINTER(c_i64)],
+    "ink_mask_small_regions": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p],
+    "ink_box_nms": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "ink_ms_deform_attn_forward": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), c_void_p, c_void_p, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_ms_deform_attn_forward_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -33,8 +33,10 @@ def _newest_header() -> float:
 # Kernels whose LDS fragment reads are volatile asm with hand-counted waits (ffn_fused.hip, proj_ln.hip): the compiler
 # does not know that such a read completes later, so a SPILL of its destination register would store the register
 # before the data has arrived (round 3: NaNs from a 32-byte spill).  Their build fails unless every kernel of the file
-# reports zero scratch.
-NO_SPILL = {"ffn_fused.hip", "proj_ln.hip"}
+# reports zero scratch.  amg.hip is held to the same report for another reason: its mask-statistics kernel keeps a
+# thread's column state and bit words in registers across a whole band of rows, and scratch traffic there would put it
+# back behind the memory system it exists to avoid.
+NO_SPILL = {"ffn_fused.hip", "proj_ln.hip", "amg.hip"}
 
 
 def _check_no_spill(src: Path, remarks: str) -> None:
@@ -45,8 +47,8 @@ def _check_no_spill(src: Path, remarks: str) -> None:
         elif "ScratchSize [bytes/lane]:" in line:
             n = int(line.split("ScratchSize [bytes/lane]:")[1].split("[")[0])
             if n != 0:
-                raise RuntimeError(f"{src.name}: kernel {name} spills ({n} bytes of scratch per lane) - its asm LDS reads "
-                                   f"are not spill-safe; reduce register pressure")
+                raise RuntimeError(f"{src.name}: kernel {name} spills ({n} bytes of scratch per lane) - the kernels of "
+                                   f"this file must stay in registers (see NO_SPILL); reduce register pressure")
 
 
 def _compile(src: Path, force: bool, hdr_time: float) -> Path:
@@ -66,7 +68,8 @@ def _compile(src: Path, force: bool, hdr_time: float) -> Path:
         except RuntimeError:
             obj.unlink(missing_ok=True)
             raise
-        err = "\n".join(l for l in err.splitlines() if "kernel-resource-usage" not in l)
+        err = "\n".join(l for l in err.splitlines()
+                        if "kernel-resource-usage" not in l and not l.startswith("In file included from"))
     if err.strip():
         sys.stderr.write(err)
     return obj

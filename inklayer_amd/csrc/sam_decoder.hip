@@ -1,5 +1,6 @@
 // SAM prompt-encoder / mask-decoder tail kernels (small, HBM/latency bound).
 #include "common.h"
+#include "sam_postprocess.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
@@ -229,45 +230,20 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(const float* __restric
   out[((int64_t)b * 4 * g + Y) * 4 * g + X] = acc;
 }
 
-// torch bilinear (align_corners=False) source index + weights
-__device__ __forceinline__ void bil(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-  i1 = i0 < in_size - 1 ? i0 + 1 : i0;
-  l1 = src - (float)i0;
-}
-
 // Sam.postprocess_masks + threshold, fused: low [n, S, S] -> (virtual) [L, L] -> crop
 // [in_h, in_w] -> [out_h, out_w] -> (> thr) as uint8.  Nothing but the bool mask is written.
+// The per-pixel arithmetic is post_pixel / post_cols + post_row of sam_postprocess.h.
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ low, int n, int S,
                                                           int L, int in_h, int in_w, int out_h,
                                                           int out_w, float thr,
                                                           uint8_t* __restrict__ out,
                                                           float* __restrict__ out_logits) {
   const int64_t total = (int64_t)n * out_h * out_w;
-  const float sA = (float)S / (float)L;
-  const float sBh = (float)in_h / (float)out_h, sBw = (float)in_w / (float)out_w;
+  const PostScales sc = post_scales(S, L, in_h, in_w, out_h, out_w);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int X = (int)(i % out_w), Y = (int)((i / out_w) % out_h);
     const int b = (int)(i / ((int64_t)out_w * out_h));
-    const float* lp = low + (int64_t)b * S * S;
-    int y0, y1, x0, x1;
-    float ly, lx;
-    bil(Y, sBh, in_h, y0, y1, ly);
-    bil(X, sBw, in_w, x0, x1, lx);
-    auto stageA = [&](int yy, int xx) {
-      int a0, a1, c0, c1;
-      float la, lc;
-      bil(yy, sA, S, a0, a1, la);
-      bil(xx, sA, S, c0, c1, lc);
-      const float v00 = lp[a0 * S + c0], v01 = lp[a0 * S + c1];
-      const float v10 = lp[a1 * S + c0], v11 = lp[a1 * S + c1];
-      return (1.f - la) * ((1.f - lc) * v00 + lc * v01) + la * ((1.f - lc) * v10 + lc * v11);
-    };
-    const float v00 = stageA(y0, x0), v01 = stageA(y0, x1), v10 = stageA(y1, x0), v11 = stageA(y1, x1);
-    const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+    const float v = post_pixel(low + (int64_t)b * S * S, S, sc, in_h, in_w, Y, X);
     if (out) out[i] = v > thr ? 1 : 0;
     if (out_logits) out_logits[i] = v;
   }
@@ -278,6 +254,9 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
 // INSTRUCTIONS: 2.1 M of them for 128 masks of 1024^2, 710 us), and everything that depends on the column only -
 // the second-stage source columns and weights and, for each of them, the first-stage columns and weights - is
 // computed once per thread instead of once per pixel (the index/weight arithmetic was ~half of the instructions).
+// The body states post_cols + post_row of sam_postprocess.h in place: written through those functions the kernel
+// allocates 168 instead of 126 VGPRs (one wave per SIMD less), so the text stays here and amg.hip's kernels, which call
+// the functions, are held to these floats bit for bit by tests/test_amg_gpu.py.
 __global__ __launch_bounds__(256) void postprocess_rows_kernel(const float* __restrict__ low, int n, int S, int L,
                                                                int in_h, int in_w, int out_h, int out_w, float thr,
                                                                uint8_t* __restrict__ out,

@@ -521,6 +521,132 @@ def sam_postprocess(low: torch.Tensor, L: int, input_hw: Tuple[int, int], orig_h
 
 
 # ---------------------------------------------------------------------------------------------
+# SamAutomaticMaskGenerator's tail (inklayer_amd/amg.py)
+# ---------------------------------------------------------------------------------------------
+NMS_MAX_BOXES = 4096
+
+
+def sam_amg_stats(low: torch.Tensor, L: int, input_hw: Tuple[int, int], crop_hw: Tuple[int, int], thr: float,
+                  offset: float, xy0: Tuple[int, int] = (0, 0), orig_hw: Optional[Tuple[int, int]] = None,
+                  index: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                  want_logits: bool = False):
+    """low [n, S, S] f32 -> (table int32 [m, 8], planes int64 [m, W, ceil(H / 64)]) (and the f32 logits [m, ch, cw] with
+    want_logits, a test hook): per mask count(v > thr + offset), count(v > thr - offset), count(v > thr), the box
+    x_min, y_min, x_max, y_max of v > thr in crop coordinates, 0; and v > thr as a column-major bit plane of the
+    orig_hw frame with the crop at xy0.  v = postprocess_masks(low) at crop_hw, the floats of sam_postprocess.
+    index int32 [m] (device) selects and orders the masks; count int32 [1] (device) processes only its first `count`
+    entries (the other table rows are zero, the other planes unwritten), so a filter made on the device needs no host round trip."""
+    assert low.dtype == F32 and low.is_contiguous() and low.dim() == 3
+    n, S, _ = low.shape
+    ch, cw = crop_hw
+    oh, ow = orig_hw if orig_hw is not None else crop_hw
+    if index is not None:
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+    if count is not None:
+        assert count.dtype == torch.int32 and count.is_cuda and count.numel() == 1
+    m = n if index is None else index.numel()
+    hp = -(-oh // 64)
+    table = torch.empty((m, 8), device=low.device, dtype=torch.int32)
+    planes = torch.empty((m, ow, hp), device=low.device, dtype=torch.int64)
+    lg = torch.empty((m, ch, cw), device=low.device, dtype=F32) if want_logits else None
+    if m > 0:
+        check(_lib.lib().ink_sam_amg_stats(low.data_ptr(), n, _p(index), m, _p(count), S, L, input_hw[0], input_hw[1],
+                                           ch, cw, thr, offset, xy0[0], xy0[1], oh, ow, table.data_ptr(),
+                                           planes.data_ptr(), _p(lg), _stream()), "ink_sam_amg_stats")
+    return (table, planes, lg) if want_logits else (table, planes)
+
+
+def mask_rle(planes: torch.Tensor, H: int, W: int, select: Optional[torch.Tensor] = None):
+    """Column-major bit planes int64 [m, W, ceil(H / 64)] -> the `counts` lists of mask_to_rle_pytorch
+    (SA/utils/amg.py:107-135) for the planes select[0..k) (all of them when None).  Two launches with the size
+    read-back between them; nothing is launched for k == 0."""
+    assert planes.dtype == torch.int64 and planes.is_cuda and planes.is_contiguous()
+    assert planes.dim() == 3 and tuple(planes.shape[1:]) == (W, -(-H // 64))
+    if select is not None:
+        assert select.dtype == torch.int32 and select.is_cuda and select.is_contiguous() and select.dim() == 1
+    k = planes.shape[0] if select is None else select.numel()
+    if k == 0:
+        return []
+    nc = torch.empty((k,), device=planes.device, dtype=torch.int32)
+    check(_lib.lib().ink_mask_rle_counts(planes.data_ptr(), _p(select), k, H, W, nc.data_ptr(), _stream()),
+          "ink_mask_rle_counts")
+    sizes = nc.cpu()
+    ends = torch.cumsum(sizes.long(), 0)
+    total = int(ends[-1])
+    assert total < 2 ** 31
+    offs = (ends - sizes).to(torch.int32).to(planes.device)
+    counts = torch.empty((total,), device=planes.device, dtype=torch.int32)
+    check(_lib.lib().ink_mask_rle_write(planes.data_ptr(), _p(select), k, H, W, offs.data_ptr(), counts.data_ptr(),
+                                        _stream()), "ink_mask_rle_write")
+    return [c.tolist() for c in torch.split(counts.cpu(), sizes.tolist())]
+
+
+def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """torchvision.ops.nms for one category: boxes f32 [n, 4] xyxy, scores f32 [n] (no NaN) -> int64 indices of the
+    kept boxes in descending score order, ties in score to the lower index.  n <= NMS_MAX_BOXES."""
+    assert boxes.dtype == F32 and boxes.is_cuda and boxes.is_contiguous() and boxes.dim() == 2 and boxes.shape[1] == 4
+    assert scores.dtype == F32 and scores.is_cuda and scores.is_contiguous() and scores.shape == boxes.shape[:1]
+    n = boxes.shape[0]
+    if n > NMS_MAX_BOXES:
+        raise ValueError(f"box_nms serves at most {NMS_MAX_BOXES} boxes, got {n}")
+    if n == 0:
+        return torch.empty((0,), device=boxes.device, dtype=torch.int64)
+    ws = torch.empty((n * (-(-n // 64) + 3),), device=boxes.device, dtype=torch.int64)
+    keep = torch.empty((n + 1,), device=boxes.device, dtype=torch.int32)
+    check(_lib.lib().ink_box_nms(boxes.data_ptr(), scores.data_ptr(), n, iou_threshold, ws.data_ptr(), keep.data_ptr(),
+                                 keep[n:].data_ptr(), _stream()), "ink_box_nms")
+    host = keep.cpu()
+    return host[:int(host[n])].long().to(boxes.device)
+
+
+def pack_col_planes(masks: torch.Tensor) -> torch.Tensor:
+    """bool / uint8 masks [k, H, W] on the device -> column-major bit planes int64 [k, W, ceil(H / 64)] (pixel != 0):
+    ink_bitplane_pack on the transposed images."""
+    assert masks.is_cuda and masks.dim() == 3 and masks.dtype in (torch.bool, torch.uint8)
+    k, H, W = masks.shape
+    t = masks.to(torch.uint8).transpose(1, 2).contiguous()
+    planes = torch.empty((k, W, -(-H // 64)), device=masks.device, dtype=torch.int64)
+    if k:
+        check(_lib.lib().ink_bitplane_pack(t.data_ptr(), k, W, H, 0, planes.data_ptr(), _stream()), "ink_bitplane_pack")
+    return planes
+
+
+def remove_small_regions(planes: torch.Tensor, H: int, W: int, min_area: int, max_workspace_bytes: int = 1 << 29,
+                         modes: Sequence[str] = ("holes", "islands")) -> Tuple[torch.Tensor, torch.Tensor]:
+    """remove_small_regions(mode="holes") then (mode="islands") of SA/utils/amg.py:267-291, as postprocess_small_regions
+    applies them, on column-major planes int64 [k, W, ceil(H / 64)] -> (cleaned planes, changed bool [k] = either pass
+    found a region below min_area); `modes` runs one of the passes alone.  The planes go through in chunks whose
+    component workspace stays below max_workspace_bytes (it is sized for the true run bound, 7 ints per possible run)."""
+    assert planes.dtype == torch.int64 and planes.is_cuda and planes.is_contiguous()
+    assert planes.dim() == 3 and tuple(planes.shape[1:]) == (W, -(-H // 64))
+    k = planes.shape[0]
+    out = torch.empty_like(planes)
+    changed = torch.zeros((k,), device=planes.device, dtype=torch.int32)
+    if k == 0:
+        return out, changed.bool()
+    L = _lib.lib()
+    one = C.c_int64(0)
+    check(L.ink_mask_small_regions_workspace_ints(1, H, W, C.byref(one)), "ink_mask_small_regions_workspace_ints")
+    chunk = max(1, min(k, max_workspace_bytes // (4 * one.value)))
+    need = C.c_int64(0)
+    check(L.ink_mask_small_regions_workspace_ints(chunk, H, W, C.byref(need)), "ink_mask_small_regions_workspace_ints")
+    ws = torch.empty((need.value,), device=planes.device, dtype=torch.int32)
+    tmp = torch.empty_like(planes[:chunk])
+    flag = torch.empty((chunk,), device=planes.device, dtype=torch.int32)
+    for a in range(0, k, chunk):
+        n = min(chunk, k - a)
+        src, dst = planes[a:a + n], out[a:a + n]
+        for j, mode in enumerate(modes):
+            assert mode in ("holes", "islands")
+            holes = int(mode == "holes")
+            check(L.ink_mask_small_regions((dst if j else src).data_ptr(), n, H, W, int(min_area), holes,
+                                           tmp.data_ptr(), ws.data_ptr(), dst.data_ptr(), flag.data_ptr(), _stream()),
+                  "ink_mask_small_regions")
+            changed[a:a + n] |= flag[:n]
+    return out, changed.bool()
+
+
+# ---------------------------------------------------------------------------------------------
 # GroundingDINO-side ops
 # ---------------------------------------------------------------------------------------------
 _MSDA_DTYPE = {F32: 0, torch.float64: 1}

@@ -1067,3 +1067,12 @@ def run_SAM(image_pil, boxes_filt: torch.Tensor, sam_checkpoint: Optional[str] =
     masks, _, _ = pred.predict_torch(None, None, boxes=tb, multimask_output=False)
     m = masks[:, 0].cpu().numpy()                          # ONE device->host copy for all boxes
     return [m[i] for i in range(m.shape[0])]
+
+
+def __getattr__(name):
+    # SamAutomaticMaskGenerator lives in inklayer_amd/amg.py (which imports this module) and is offered here too, next
+    # to SamPredictor, where the reference's package offers it
+    if name == "SamAutomaticMaskGenerator":
+        from .amg import SamAutomaticMaskGenerator
+        return SamAutomaticMaskGenerator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
