@@ -306,71 +306,3 @@ def glob_ref(q, k, v, rh, rw, *, drop_tile=None, last_tile_rows=False, swap=Fals
     o, P, s = attn_ref(q, k, v, bias)
     return o, P, s, bmag
 
-
-# ---------------------------------------------------------------------------------------------------------------
-# LayerNorm folded into qkv / lin1 (ln_fold=True), fed by the statistics proj writes
-# ---------------------------------------------------------------------------------------------------------------
-def ln_fold_ref(x, wl, bias_ln, act, eps=1e-6, parts_used=None, chunk=64, uncentred=False):
-    """float64 LayerNorm (no affine) of the stream rows x [M, 1280] -> linear with the folded f16 weights wl (gamma
-    inside) + bias_ln -> act.  Mistakes: parts_used (the mean / variance from that many leading statistics chunks
-    only), uncentred (the mean colsum term left out).  Returns (out, pre-activation)."""
-    x64 = x.double()
-    xs = x64 if parts_used is None else x64[:, :parts_used * chunk]
-    mean = xs.mean(1, keepdim=True)
-    var = xs.var(1, unbiased=False, keepdim=True)
-    y = (x64 - (0 if uncentred else mean)) / torch.sqrt(var + eps) @ wl.double().t() + bias_ln.double()
-    return (torch.nn.functional.gelu(y) if act == "gelu" else y), y
-
-
-def ln_fold_tol(x, hi, lo, wl, bias_ln, colsum, out, lin, act, eps=1e-6, parts=20):
-    """gemm_f16_nt_pp EPI 1 / 2: out = act(rstd (hi w^T - mean colsum) + bias_ln) with mean / var = E[x^2] - mean^2
-    from the f32 (sum, sum of squares) of `parts` chunks.  The operand is the hi plane, not hi + lo, and the
-    f16 products are exact: that moves the result by exactly rstd |lo w^T|.  The chunk sums (<= 64 f32 roundings
-    each, of values within 2^-21 of the stream) and
-    the sum over the parts: gamma = (64 + parts + 8) u relative to sum |x| and sum x^2, so |d mean| <= 2 gamma mean|x|
-    and |d var| <= gamma E[x^2] + 2 |mean| d mean + d mean^2 + 3 u (E[x^2] + mean^2): the cancellation of a row with a
-    large |mean| / std sits here.  rstd is off by <= d var / (var + eps) + 3 u relative.  The MFMA accumulation of
-    hi w^T (as in gemm_tol: K/32 accumulator adds against the running sum, 5 levels inside each step against the
-    step's own products) and the mean colsum product / difference: (K/32 + 8) u (|hi| |w| + |mean colsum|);
-    the bias add u |y|; GELU and the f16 store as in gemm_tol."""
-    x64 = x.double()
-    K = x.shape[1]
-    mean = x64.mean(1, keepdim=True)
-    var = x64.var(1, unbiased=False, keepdim=True)
-    rstd = 1.0 / torch.sqrt(var + eps)
-    e2 = (x64 ** 2).mean(1, keepdim=True)
-    gam = (64 + parts + 8) * U
-    dmu = 2 * gam * x64.abs().mean(1, keepdim=True)
-    dvar = gam * e2 + 2 * mean.abs() * dmu + dmu ** 2 + 3 * U * (e2 + mean ** 2)
-    eps_r = dvar / (var + eps) + 3 * U
-    wa = wl.double().abs()
-    cs = colsum.double()
-    t = (rstd * ((lo.double() @ wl.double().t()).abs() + (K / 32 + 8) * U * (hi.double().abs() @ wa.t() + (mean * cs).abs())
-                 + dmu * cs.abs()) + eps_r * (lin - bias_ln.double()).abs() + U * lin.abs())
-    if act == "gelu":
-        t = 1.13 * t + (GELU_ERF / 2 + 6 * U) * lin.abs() + U * out.abs()
-    return t + H16 * out.abs() + SUB16
-
-
-def fold_stream(M, g, dev):
-    """A split-f16 stream (hi + lo planes) as the ln_fold engine keeps it: rows N(0, 1.5^2) + a per-row N(0, 0.7^2)
-    offset, rows 0-63 with an offset of +-55 (|mean| / std ~ 30 after the projection adds its N(0, 1) update).
-    Returns (hi + lo in float64, hi, lo)."""
-    x = torch.randn(M, D, generator=g, device=dev) * 1.5 + 0.7 * torch.randn(M, 1, generator=g, device=dev)
-    x[:64] += 55 * torch.sign(torch.randn(64, 1, generator=g, device=dev))
-    hi = x.half()
-    lo = (x - hi.float()).half()
-    return hi.double() + lo.double(), hi, lo
-
-
-def fold_weights(N, g, dev):
-    """The engine's folded weights of one projection (SamEngine.__init__, ln_fold=True): wl = f16(W gamma), colsum of
-    the rounded rows, bias_ln = W beta + b."""
-    W = torch.randn(N, D, generator=g, device=dev) / D ** 0.5
-    b = 0.1 * torch.randn(N, generator=g, device=dev)
-    gam = 1.0 + 0.1 * torch.randn(D, generator=g, device=dev)
-    bet = 0.1 * torch.randn(D, generator=g, device=dev)
-    wl = (W * gam[None]).half().contiguous()
-    colsum = wl.double().sum(1).float().contiguous()
-    bias_ln = (W.double() @ bet.double() + b.double()).float().contiguous()
-    return wl, bias_ln, colsum
