@@ -108,20 +108,20 @@ def swap_tiles(ref, BM=256, BN=320):
 # ---------------------------------------------------------------------------------------------------------------
 # layernorm_rows at C = 1280
 # ---------------------------------------------------------------------------------------------------------------
-def layernorm_data(R, gen, dev):
-    """R rows of 1280 with the hard cases up front: rows 0-7 a common offset of 30 std (|mean| / std = 30), rows
+def layernorm_data(R, gen, dev, C=D):
+    """R rows of C (default 1280) with the hard cases up front: rows 0-7 a common offset of 30 std (|mean| / std = 30), rows
     8-15 four 'massive' channels 100x the rest, rows 16-19 constant (var = 0: rstd = eps^-1/2; 3.25 sums exactly),
     rows 20-23 N(0, 1) on an offset of +-3000 (where a one-pass E[x^2] - mean^2 variance in f32 is lost), the rest
     N(0.5, 3).  gamma 1 + 0.1 N and beta 0.1 N, but channels 0-63 have gamma 2^-18, beta 0 (f16-subnormal outputs)."""
-    x = 3 * torch.randn(R, D, generator=gen, device=dev) + 0.5
-    x[0:8] = torch.randn(8, D, generator=gen, device=dev) + 30 * torch.tensor([1, -1, 1, -1, 1, -1, 1, -1.0], device=dev)[:, None]
-    x[8:16] = torch.randn(8, D, generator=gen, device=dev)
-    x[8:16, [3, 700, 701, 1279]] *= 100
+    x = 3 * torch.randn(R, C, generator=gen, device=dev) + 0.5
+    x[0:8] = torch.randn(8, C, generator=gen, device=dev) + 30 * torch.tensor([1, -1, 1, -1, 1, -1, 1, -1.0], device=dev)[:, None]
+    x[8:16] = torch.randn(8, C, generator=gen, device=dev)
+    x[8:16, [3, 700, 701, C - 1]] *= 100
     x[16:20] = 3.25
-    x[20:24] = torch.randn(4, D, generator=gen, device=dev) + 3000 * torch.tensor([1, -1, 1, -1.0], device=dev)[:, None]
-    gamma = 1 + 0.1 * torch.randn(D, generator=gen, device=dev)
+    x[20:24] = torch.randn(4, C, generator=gen, device=dev) + 3000 * torch.tensor([1, -1, 1, -1.0], device=dev)[:, None]
+    gamma = 1 + 0.1 * torch.randn(C, generator=gen, device=dev)
     gamma[:64] = 2.0 ** -18
-    beta = 0.1 * torch.randn(D, generator=gen, device=dev)
+    beta = 0.1 * torch.randn(C, generator=gen, device=dev)
     beta[:64] = 0
     return x, gamma, beta
 
