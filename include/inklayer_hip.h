@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define INK_ABI_VERSION 6
+#define INK_ABI_VERSION 7
 int ink_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -381,19 +381,17 @@ int ink_fusion_fold(float* v_f32, int32_t B, int32_t S, const float* lnv_g, cons
                     void* out16, void* stream);
 
 /* Tail of the SAM mask decoder in one kernel (csrc/upscale_tail.hip): LayerNorm2d + GELU + the second ConvTranspose2d
- * (k2 s2 = a [64 -> 4 x 32] projection per row) + GELU + the hyper-network product of mask token 0
- * (SA/modeling/mask_decoder.py:54-60, 138-145).  u0 f32: the first transposed convolution's output, 4 x 64 floats per
+ * (k2 s2 = a [64 -> 4 x 32] projection per row) + GELU + the hyper-network product of n_masks in {1, 3, 4}
+ * mask tokens per box (SA/modeling/mask_decoder.py:54-60, 138-145; the upscaling is computed once per row and shared by
+ * the masks, and mask m of a 4-mask call equals a 1-mask call with hyper vector m bit for bit).  u0 f32: the first transposed convolution's output, 4 x 64 floats per
  * (box, token) at token stride ld_tok (>= 256 floats: it may be a column block of a wider projection), row (token, s1); ln_g / ln_b f32 [64] (output_upscaling.1), eps 1e-6; blob: output_upscaling.3.weight as the
  * split-f16 matrix [128, 192] (rows (s2, c), see ink_add_split_f16) packed by ink_sam_upscale_pack (48 KiB); b3 f32 [128]
- * (the bias repeated per sub-pixel); hyper f32 [n, 32]; low f32 [n, 4g, 4g].  (g*g*4) % 32 == 0. */
+ * (the bias repeated per sub-pixel); hyper f32 [n, n_masks, 32]; low f32 [n, n_masks, 4g, 4g].
+ * (g*g*4) % 32 == 0. */
 int ink_sam_upscale_pack(const void* ws_f16, void* blob_f16, void* stream);
 int ink_sam_upscale_tail(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const float* ln_g, const float* ln_b, float eps,
-                         const void* blob_f16, const float* b3, const float* hyper, float* low, void* stream);
-/* The same for n_masks in {1, 3, 4} mask tokens per box (multimask output): hyper f32 [n, n_masks, 32], low f32
- * [n, n_masks, 4g, 4g].  Mask 0 of a 4-mask call equals ink_sam_upscale_tail bit for bit; n_masks = 1 is that call. */
-int ink_sam_upscale_tail_masks(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const float* ln_g,
-                               const float* ln_b, float eps, const void* blob_f16, const float* b3, const float* hyper,
-                               int32_t n_masks, float* low, void* stream);
+                         const void* blob_f16, const float* b3, const float* hyper, int32_t n_masks, float* low,
+                         void* stream);
 
 /* Image-side tail of a layer of SAM's two-way transformer in one kernel (csrc/proj_ln.hip):
  *     out = LayerNorm(res + a W^T + bias)         a f32 [rows, 128] (the image->token attention's output), 256 columns

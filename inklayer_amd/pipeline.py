@@ -244,6 +244,7 @@ class InkLayerPipeline:
 
     def _decode_all(self, dets, emb, sizes) -> List[SketchResult]:
         L = self.seg.cfg.img_size
+        transform = sm.ResizeLongestSide(L)
         per_img, all_boxes, img_of_box = [], [], []
         for b, ((boxes_cxcywh, scores), ((oh, ow), (ih, iw))) in enumerate(zip(dets, sizes)):
             bx = boxes_cxcywh.double().numpy().reshape(-1, 4)
@@ -252,12 +253,7 @@ class InkLayerPipeline:
             pix = boxes_to_pixels(xyxy, ow, oh)
             per_img.append((xyxy, scores.numpy(), pix))
             if len(pix):
-                # ResizeLongestSide.apply_boxes_torch (SA/utils/transforms.py:67-91)
-                nh, nw = sm.preprocess_shape(oh, ow, L)
-                tb = pix.reshape(-1, 2, 2).clone()
-                tb[..., 0] = tb[..., 0] * (nw / ow)
-                tb[..., 1] = tb[..., 1] * (nh / oh)
-                all_boxes.append(tb.reshape(-1, 4))
+                all_boxes.append(transform.apply_boxes_torch(pix, (oh, ow)))
                 img_of_box += [b] * len(pix)
         # prompt encoder + mask decoder for ALL boxes of the batch in one pass
         low = None

@@ -250,8 +250,6 @@ class SamEngine:
 
         # ---- prompt encoder constants
         w["gauss"] = f("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix")
-        w["corner"] = torch.cat([f("prompt_encoder.point_embeddings.2.weight"),
-                                 f("prompt_encoder.point_embeddings.3.weight")], 0).contiguous()
         w["no_mask"] = f("prompt_encoder.no_mask_embed.weight").reshape(-1).contiguous()
         # point and mask prompts (SamEngine.decode_prompts).  A state dict made for the box path alone may lack these
         # weights: they are then absent here and decode_prompts names what is missing.
@@ -515,19 +513,9 @@ class SamEngine:
         """Prompt encoder + mask decoder for N boxes spread over B images in ONE pass (the reference decodes
         one image at a time; batching only changes which rows share a launch).  emb [B, 4096, 256] f32,
         boxes [N, 4] xyxy in the resized-input frame (host), img_of_box[i] = image of box i.
-        -> (low-res logits [N, 256, 256] f32, iou [N, 1] f32)."""
-        cfg, w, dev = self.cfg, self.w, self.dev
-        E, L = cfg.prompt_embed_dim, cfg.img_size
-        n = boxes.shape[0]
-        assert n > 0 and len(img_of_box) == n
-        NT = 5 + 2
-        coords = _to_dev_async((boxes + 0.5).reshape(-1, 2) / float(L), dev)
-        sparse = ops.sam_pe_encode(coords, w["gauss"], add=w["corner"])           # [2n, E]
-        tokens = torch.empty((n, NT, E), device=dev, dtype=F32)
-        tokens[:, :5] = w["out_tok"]
-        tokens[:, 5:] = sparse.view(n, 2, E)
-        low, iou = self._decode_tokens_split(emb, tokens, img_of_box)
-        return low.view(n, *low.shape[-2:]), iou
+        -> (low-res logits [N, 256, 256] f32, iou [N, 1] f32).  decode_prompts with boxes alone and mask token 0."""
+        low, iou = self.decode_prompts(emb, img_of_box, boxes=boxes)
+        return low.view(low.shape[0], *low.shape[-2:]), iou
 
     def decode_prompts(self, emb: torch.Tensor, img_of_prompt: Sequence[int], points: Optional[torch.Tensor] = None,
                        labels: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None,
@@ -563,8 +551,10 @@ class SamEngine:
             pts, lab = dev32(points), dev32(labels, torch.int32)
         if boxes is not None:
             bx = dev32(torch.as_tensor(boxes).reshape(-1, 4))
-        tokens = ops.sam_prompt_tokens(w["gauss"], w["pt_emb"], w["not_a_point"], w["out_tok"], float(L), P, points=pts,
-                                       labels=lab, boxes=bx, pad=points is not None and boxes is None)
+        # not_a_point is read for points alone (checked above): a state dict made for the box path may lack it
+        tokens = ops.sam_prompt_tokens(w["gauss"], w["pt_emb"], w.get("not_a_point", w["no_mask"]), w["out_tok"],
+                                       float(L), P, points=pts, labels=lab, boxes=bx,
+                                       pad=points is not None and boxes is None)
         mi = dev32(mask_input) if mask_input is not None else None
         return self._decode_tokens_split(emb, tokens, img_of_prompt, mask_input=mi, mask_lo=lo, n_masks=M)
 
@@ -660,20 +650,16 @@ class SamEngine:
             return lin(SP(a), prefix + "2")
 
         M = n_masks
-        if mask_lo == 0 and M == 1:
-            hyper = mlp3("hyp", hs[:, 1].contiguous())      # mask token 0 -> [n, 32]
+        if M == 1:                                          # a view: one mask token costs no launch here
+            hyper = mlp3(_hyp(mask_lo), hs[:, 1 + mask_lo].contiguous()).view(n, 1, 32)
         else:                                               # tokens mask_lo .. mask_lo + M - 1 -> [n, M, 32]
             hyper = torch.stack([mlp3(_hyp(m), hs[:, 1 + m].contiguous()) for m in range(mask_lo, mask_lo + M)], 1)
         iou = mlp3("iou", hs[:, 0].contiguous())[:, mask_lo:mask_lo + M]     # iou token -> [n, 4] -> the M masks
         u0 = kvu[:, 2 * Eh:]                                                     # [n*T, 4*64], row stride 512
         # LayerNorm2d + GELU + the second transposed convolution + GELU + the hyper-network product in one kernel
         # (csrc/upscale_tail.hip): u0 is read once, 4 floats per row and mask are written
-        if M == 1:
-            low = ops.sam_upscale_tail(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"],
-                                       hyper.reshape(n, 32).contiguous())
-        else:
-            low = ops.sam_upscale_tail_masks(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"], hyper)
-        return low.view(n, M, 4 * g, 4 * g), iou
+        low = ops.sam_upscale_tail(u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"], hyper)
+        return low, iou
 
 
 # ----------------------------------------------------------------------------------------
@@ -711,12 +697,7 @@ class SamPredictor:
 
     def apply_boxes(self, boxes: torch.Tensor) -> torch.Tensor:
         """ResizeLongestSide.apply_boxes_torch (SA/utils/transforms.py:67-91), host side."""
-        oh, ow = self.original_size
-        nh, nw = preprocess_shape(oh, ow, self.cfg.img_size)
-        c = boxes.detach().cpu().reshape(-1, 2, 2).clone().to(torch.float)
-        c[..., 0] = c[..., 0] * (nw / ow)
-        c[..., 1] = c[..., 1] * (nh / oh)
-        return c.reshape(-1, 4)
+        return self.transform.apply_boxes_torch(boxes.detach().cpu(), self.original_size)
 
     def apply_coords(self, coords: np.ndarray, original_size: Optional[Tuple[int, int]] = None) -> np.ndarray:
         """ResizeLongestSide.apply_coords (SA/utils/transforms.py:33-45): original-image pixels -> input frame."""
@@ -753,14 +734,6 @@ class SamPredictor:
         return_logits), iou [B, C], low-res logits [B, C, 256, 256]); C = 3 with multimask_output, else 1."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        if point_coords is None and point_labels is None and mask_input is None and not multimask_output \
-                and boxes is not None:
-            # box prompts, mask token 0: InkLayer's call (decode_low_res)
-            masks, low, iou, logits = self.engine.decode(self.features, boxes.detach().cpu(), self.input_size,
-                                                         self.original_size, want_logits=True)
-            n = masks.shape[0]
-            out = logits if return_logits else masks.bool()
-            return out.view(n, 1, *self.original_size), iou, low.view(n, 1, *low.shape[-2:])
         eng = self.engine
         P, _ = check_prompts(point_coords, point_labels, boxes, mask_input, mask_side=4 * self.cfg.grid)
         low, iou = eng.decode_prompts(self.features.reshape(1, eng.T, -1), [0] * P, point_coords, point_labels, boxes,

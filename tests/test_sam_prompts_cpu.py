@@ -111,9 +111,9 @@ def test_new_exports_reject_bad_arguments_without_launch():
     mcall = lambda **kw: l.ink_sam_mask_embed(*{**margs, **kw}.values(), None)
     assert mcall(n_prm=4683) == 1 and mcall(g=65) == 1 and mcall(keys=20) == 1 and mcall(rows=None) == 1
     assert mcall(split=18) == 1 and mcall(P=0) == 1
-    # ink_sam_upscale_tail_masks: mask counts other than 1, 3, 4; bad ld_tok
+    # ink_sam_upscale_tail: mask counts other than 1, 3, 4; bad ld_tok
     uargs = dict(u0=p, ld=512, n=1, g=64, lg=p, lb=p, eps=1e-6, blob=p, b3=p, hyper=p, M=3, low=p)
-    ucall = lambda **kw: l.ink_sam_upscale_tail_masks(*{**uargs, **kw}.values(), None)
+    ucall = lambda **kw: l.ink_sam_upscale_tail(*{**uargs, **kw}.values(), None)
     assert ucall(M=2) == 1 and ucall(M=5) == 1 and ucall(M=0) == 1 and ucall(ld=100) == 1 and ucall(low=None) == 1
     # ink_attn_fewq: more than 16 queries; 9..16 queries need f32 rows
     fargs = dict(Q=p, ldq=128, K=p, ldk=128, V=p, ldv=128, nb=1, nq=9, nk=4096, nh=8, hd=16, scale=0.25, qr=None,

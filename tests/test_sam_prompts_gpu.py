@@ -122,13 +122,26 @@ def test_box_plus_mask_input_match_restatement(dev, eng_sd, embs, multimask):
 
 @torch.no_grad()
 def test_box_prompts_general_entry_is_bitwise_decode_low_res(dev, eng_sd, embs):
+    """decode_low_res is decode_prompts with boxes alone; both must give the bits of the box path as it was before the
+    general entry existed: the output tokens copied in front of sam_pe_encode(add=corner embeddings) of host-normalised
+    corners, through the same decoder."""
+    from inklayer_amd import ops
     eng, oc, sd64 = eng_sd
+    w, n = eng.w, BOXES.shape[0]
     img = [0, 1, 1]
+    coords = ((BOXES + 0.5).reshape(-1, 2) / 1024.0).to(dev)
+    tokens = torch.empty((n, 7, 256), device=dev)
+    tokens[:, :5] = w["out_tok"]
+    tokens[:, 5:] = ops.sam_pe_encode(coords, w["gauss"], add=w["pt_emb"][2:4]).view(n, 2, 256)
+    o_low, o_iou = eng._decode_tokens_split(embs.to(dev), tokens, img)
     a_low, a_iou = eng.decode_low_res(embs.to(dev), BOXES, img)
+    assert torch.equal(a_low, o_low[:, 0]) and torch.equal(a_iou, o_iou)
     b_low, b_iou = eng.decode_prompts(embs.to(dev), img, None, None, BOXES)
-    assert torch.equal(a_low, b_low[:, 0]) and torch.equal(a_iou, b_iou)
+    assert torch.equal(b_low, o_low) and torch.equal(b_iou, o_iou)
     b_low, b_iou = eng.decode_prompts(embs.to(dev), img, None, None, BOXES.to(dev))   # prompts already on the device
-    assert torch.equal(a_low, b_low[:, 0]) and torch.equal(a_iou, b_iou)
+    assert torch.equal(b_low, o_low) and torch.equal(b_iou, o_iou)
+    a_low, a_iou = eng.decode_low_res(embs.to(dev), BOXES.to(dev), img)
+    assert torch.equal(a_low, o_low[:, 0]) and torch.equal(a_iou, o_iou)
 
 
 @torch.no_grad()
@@ -195,12 +208,13 @@ def test_prompt_tokens_op(dev, eng_sd):
     from inklayer_amd import ops
     eng, oc, sd64 = eng_sd
     w = eng.w
-    # box-only: the same bits as sam_pe_encode(add=corner) behind the copied output tokens (today's box path)
+    # box-only: the same bits as sam_pe_encode(add=corner embeddings) behind the copied output tokens (the box path before
+    # this op)
     n = BOXES.shape[0]
     coords = ((BOXES + 0.5).reshape(-1, 2) / 1024.0).to(dev)
     old = torch.empty((n, 7, 256), device=dev)
     old[:, :5] = w["out_tok"]
-    old[:, 5:] = ops.sam_pe_encode(coords, w["gauss"], add=w["corner"]).view(n, 2, 256)
+    old[:, 5:] = ops.sam_pe_encode(coords, w["gauss"], add=w["pt_emb"][2:4]).view(n, 2, 256)
     new = ops.sam_prompt_tokens(w["gauss"], w["pt_emb"], w["not_a_point"], w["out_tok"], 1024.0, n, boxes=BOXES.to(dev))
     assert torch.equal(old, new)
     # points (+ pad), labels -1 / 0 / 1 / 2, against float64
@@ -249,14 +263,13 @@ def test_upscale_tail_masks_op(dev, eng_sd):
     u0 = torch.from_numpy(rs.standard_normal((n * g * g, 512)).astype(np.float32)).to(dev)[:, 256:]
     hyper = torch.from_numpy(rs.standard_normal((n, 4, 32)).astype(np.float32)).to(dev)
     args = (u0, n, g, w["up1.w"], w["up1.b"], 1e-6, w["up3.blob"], w["up3.b"])
-    four = ops.sam_upscale_tail_masks(*args, hyper)
-    three = ops.sam_upscale_tail_masks(*args, hyper[:, 1:].contiguous())
-    one = ops.sam_upscale_tail_masks(*args, hyper[:, :1].contiguous())
-    single = ops.sam_upscale_tail(*args, hyper[:, 0].contiguous())
-    assert four.shape == (n, 4, 256, 256)
-    assert torch.equal(four[:, 0], single) and torch.equal(one[:, 0], single) and torch.equal(four[:, 1:], three)
+    four = ops.sam_upscale_tail(*args, hyper)
+    three = ops.sam_upscale_tail(*args, hyper[:, 1:].contiguous())
+    one = ops.sam_upscale_tail(*args, hyper[:, :1].contiguous())
+    assert four.shape == (n, 4, 256, 256) and three.shape == (n, 3, 256, 256) and one.shape == (n, 1, 256, 256)
+    assert torch.equal(four[:, :1], one) and torch.equal(four[:, 1:], three)
     for m in range(1, 4):        # mask m of the 4-mask launch = a single-mask launch with hyper vector m
-        assert torch.equal(four[:, m], ops.sam_upscale_tail(*args, hyper[:, m].contiguous()))
+        assert torch.equal(four[:, m:m + 1], ops.sam_upscale_tail(*args, hyper[:, m:m + 1].contiguous()))
 
 
 @torch.no_grad()

@@ -63,7 +63,7 @@ def main():
     pl_blob = ops.proj256_ln_pack(ops.split_weight(rn(256, 128) / 11))
     u0 = rn(n_box * T, 256)
     up_blob = ops.sam_upscale_pack(ops.split_weight(rn(128, 64) / 8))
-    hyper = rn(n_box, 32)
+    hyper = rn(n_box, 1, 32)
     b3 = rn(128)
     g64, b64 = rn(64), rn(64)
     q7 = rn(n_box * 7, 128)
