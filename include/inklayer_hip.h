@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define INK_ABI_VERSION 7
+#define INK_ABI_VERSION 8
 int ink_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -338,8 +338,8 @@ int ink_biattn_fusion(const void* QV_f16, const void* KL_f16, int32_t B, int32_t
                       void* out_v_f16, void* out_l_f16, void* stream);
 
 /* softmax(scale q k^T [+ blocked -> -inf]) v against n_k <= 16 keys; head h at columns
- * [h*hd,(h+1)*hd), hd in {16,32,64}; blocked: u8 [n_q, n_k] (1 = not allowed) or NULL.  io_f32 = 0: Q/K/V/O are
- * f16 rows, 1: f32 rows (ld* in elements either way; the math is f32 in both).  q_batch_rows (int32 [B] or NULL):
+ * [h*hd,(h+1)*hd); blocked: u8 [n_q, n_k] (1 = not allowed) or NULL.  io_f32 = 0: Q/K/V/O are f16 rows, hd in {32,64};
+ * 1: f32 rows, hd in {16,32} (ld* in elements either way; the math is f32 in both).  q_batch_rows (int32 [B] or NULL):
  * first Q row of batch entry b (default b*n_q); keys and the output are dense.  q_add (f32 [n_q, n_heads*hd] or NULL) is
  * added to the query rows by position (the per-position constant pe.W of a projection of x + pe).
  * Text self-attention (transformer_vanilla.py:114-116), decoder text cross-attention (transformer.py:893-900) and,
@@ -351,14 +351,13 @@ int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
                      int64_t ldo, void* stream);
 
 /* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
- * image: 7..16 x 4096, SA/modeling/transformer.py:163-168): head h at columns [h*hd,(h+1)*hd),
- * hd in {16,32}; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].  io_f32 = 0: f16 rows,
- * 1: f32 rows (head_dim 16 with n_heads % 4 == 0 only).  n_q > 8 needs f32 rows.  k_add (f32 [n_k, n_heads*hd] or
- * NULL, f32 rows only) is added to the key rows by key position. */
+ * image: 7..16 x 4096, SA/modeling/transformer.py:163-168) on f32 rows: head h at columns [h*hd,(h+1)*hd), head_dim
+ * must be 16 and n_heads a multiple of 4; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].
+ * k_add (f32 [n_k, n_heads*hd] or NULL) is added to the key rows by key position. */
 int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                   int32_t n_batch, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale,
-                  const int32_t* q_batch_rows, const int32_t* kv_batch_rows, const float* k_add, int32_t io_f32, void* O,
-                  int64_t ldo, void* stream);
+                  const int32_t* q_batch_rows, const int32_t* kv_batch_rows, const float* k_add, void* O, int64_t ldo,
+                  void* stream);
 
 /* Column (max, sum-exp) over the S rows of B score matrices [S, HT] f32 (HT <= 16): stats f32 [B, HT, 2];
  * part_ws f32 [B * ceil(S / 512) * HT * 2].  The text-side softmax statistics of the fusion layer. */

@@ -108,7 +108,7 @@ SIGNATURES = {
     "ink_attn_fewkeys": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
                          c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p],
     "ink_attn_fewq": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
-                      c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p],
+                      c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "ink_topk_rowmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "ink_sine_embed4": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "ink_box_refine": [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p],

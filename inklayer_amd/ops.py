@@ -945,8 +945,8 @@ def ffn256_fused(x16: torch.Tensor, res: torch.Tensor, blob: torch.Tensor, hid: 
 def attn_fewkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n_heads: int, head_dim: int,
                  scale: float, blocked: Optional[torch.Tensor] = None, n_q: Optional[int] = None,
                  q_batch_rows: Optional[torch.Tensor] = None, q_add: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Attention against n_k <= 16 keys per batch entry; q/k/v/out are all f16 or all f32 rows (f32 math either
-    way).  q_batch_rows: first q row of each batch entry (then n_q must be given)."""
+    """Attention against n_k <= 16 keys per batch entry; q/k/v/out are all f16 (head_dim 32, 64) or all f32 rows
+    (head_dim 16, 32); f32 math either way.  q_batch_rows: first q row of each batch entry (then n_q must be given)."""
     io = q.dtype
     for t in (q, k, v):
         assert t.dtype == io and io in (F16, F32) and t.dim() == 2 and t.stride(1) == 1
@@ -970,17 +970,16 @@ def attn_fewkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n
 def attn_fewq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: int, n_heads: int, head_dim: int,
               scale: float, n_q: int, n_k: int, q_batch_rows: Optional[torch.Tensor] = None,
               kv_batch_rows: Optional[torch.Tensor] = None, k_add: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Few queries (<= 8; <= 16 with f32 rows) against many keys; same row conventions as flash_attn.  q/k/v/out all
-    f16 or all f32."""
-    io = q.dtype
+    """Few queries (<= 16) against many keys on f32 rows (head_dim 16, n_heads % 4 == 0); same row conventions as
+    flash_attn."""
     for t in (q, k, v):
-        assert t.dtype == io and io in (F16, F32) and t.dim() == 2 and t.stride(1) == 1
-    out = torch.empty((n_batch * n_q, n_heads * head_dim), device=q.device, dtype=io)
+        assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1
+    out = torch.empty((n_batch * n_q, n_heads * head_dim), device=q.device, dtype=F32)
     if k_add is not None:
-        assert io == F32 and k_add.dtype == F32 and k_add.is_contiguous() and tuple(k_add.shape) == (n_k, n_heads * head_dim)
+        assert k_add.dtype == F32 and k_add.is_contiguous() and tuple(k_add.shape) == (n_k, n_heads * head_dim)
     check(_lib.lib().ink_attn_fewq(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
                                    n_batch, n_q, n_k, n_heads, head_dim, scale, _p(q_batch_rows),
-                                   _p(kv_batch_rows), _p(k_add), int(io == F32), out.data_ptr(), out.stride(0), _stream()),
+                                   _p(kv_batch_rows), _p(k_add), out.data_ptr(), out.stride(0), _stream()),
           "ink_attn_fewq")
     return out
 

@@ -79,30 +79,36 @@ def test_attn_fewkeys_f32_rows(dev, hd, heads, nq, nk):
         assert (got - ref).abs().max().item() < 2e-6 * max(1.0, ref.abs().max().item())
 
 
-def test_attn_fewq_f32_rows(dev):
-    """SAM decoder token -> image attention (7 x 4096, 8 heads x 16) on f32 rows, shared keys via kv_batch_rows and a
-    ragged key count (4096 and 4000: the masked tail of the last 64-key tile)."""
+@pytest.mark.parametrize("shared", [False, True], ids=["own", "shared"])
+@pytest.mark.parametrize("nq", [5, 7, 8])
+@pytest.mark.parametrize("heads", [8, 4])
+@pytest.mark.parametrize("nk", [4096, 4000, 1000, 300, 40])
+def test_attn_fewq_f32_rows(dev, nk, heads, nq, shared):
+    """SAM decoder token -> image attention (5..8 tokens x up to 4096 keys, head_dim 16) on f32 rows against float64,
+    3 batch entries with their own keys or sharing those of 2 images through kv_batch_rows.  4000, 1000 and 300 keys
+    leave a ragged last 64-key tile in the second wave group and 40 leave that group no keys at all; 4 heads is a
+    single head group; 5 tokens (a mask-only prompt) leave inactive query slots in a wave."""
     from inklayer_amd import ops
     g = torch.Generator(device="cpu").manual_seed(9)
-    heads, hd, nq = 8, 16, 7
+    hd, n = 16, 3
     E = heads * hd
-    for nk in (4096, 4000):
-        n_img, n = 2, 3
-        q = torch.randn(n * nq, E, generator=g)
-        k = torch.randn(n_img * nk, E, generator=g) * 2
-        v = torch.randn(n_img * nk, E, generator=g)
-        img_of = [1, 0, 1]
-        rows = torch.tensor([i * nk for i in img_of], dtype=torch.int32, device=dev)
-        out = ops.attn_fewq(q.to(dev), k.to(dev), v.to(dev), n_batch=n, n_heads=heads, head_dim=hd,
-                            scale=1 / math.sqrt(hd), n_q=nq, n_k=nk, kv_batch_rows=rows)
-        assert out.dtype == torch.float32
-        for b in range(n):
-            qb = q[b * nq:(b + 1) * nq].view(nq, heads, hd).transpose(0, 1)
-            kb = k[img_of[b] * nk:(img_of[b] + 1) * nk].view(nk, heads, hd).transpose(0, 1)
-            vb = v[img_of[b] * nk:(img_of[b] + 1) * nk].view(nk, heads, hd).transpose(0, 1)
-            ref = _attn_ref(qb, kb, vb, 1 / math.sqrt(hd)).transpose(0, 1).reshape(nq, E)
-            got = out[b * nq:(b + 1) * nq].double().cpu()
-            assert (got - ref).abs().max().item() < 5e-6 * max(1.0, ref.abs().max().item())
+    n_img, img_of = (2, [1, 0, 1]) if shared else (n, [0, 1, 2])
+    q = torch.randn(n * nq, E, generator=g)
+    k = torch.randn(n_img * nk, E, generator=g) * 2
+    v = torch.randn(n_img * nk, E, generator=g)
+    rows = torch.tensor([i * nk for i in img_of], dtype=torch.int32, device=dev) if shared else None
+    out = ops.attn_fewq(q.to(dev), k.to(dev), v.to(dev), n_batch=n, n_heads=heads, head_dim=hd,
+                        scale=1 / math.sqrt(hd), n_q=nq, n_k=nk, kv_batch_rows=rows)
+    assert out.dtype == torch.float32 and out.shape == (n * nq, E)
+    for b in range(n):
+        qb = q[b * nq:(b + 1) * nq].view(nq, heads, hd).transpose(0, 1)
+        kb = k[img_of[b] * nk:(img_of[b] + 1) * nk].view(nk, heads, hd).transpose(0, 1)
+        vb = v[img_of[b] * nk:(img_of[b] + 1) * nk].view(nk, heads, hd).transpose(0, 1)
+        ref = _attn_ref(qb, kb, vb, 1 / math.sqrt(hd)).transpose(0, 1).reshape(nq, E)
+        got = out[b * nq:(b + 1) * nq].double().cpu()
+        err, bound = (got - ref).abs().max().item(), 5e-6 * max(1.0, ref.abs().max().item())
+        print(f"n_k={nk} heads={heads} n_q={nq} shared={shared} entry {b}: max err {err:.2e} (bound {bound:.2e})")
+        assert err < bound
 
 
 def test_position_constants_and_gathered_residual(dev):

@@ -115,8 +115,12 @@ def test_new_exports_reject_bad_arguments_without_launch():
     uargs = dict(u0=p, ld=512, n=1, g=64, lg=p, lb=p, eps=1e-6, blob=p, b3=p, hyper=p, M=3, low=p)
     ucall = lambda **kw: l.ink_sam_upscale_tail(*{**uargs, **kw}.values(), None)
     assert ucall(M=2) == 1 and ucall(M=5) == 1 and ucall(M=0) == 1 and ucall(ld=100) == 1 and ucall(low=None) == 1
-    # ink_attn_fewq: more than 16 queries; 9..16 queries need f32 rows
+    # ink_attn_fewq (f32 rows): head_dim other than 16, a head count that is no multiple of 4, more than 16 queries
     fargs = dict(Q=p, ldq=128, K=p, ldk=128, V=p, ldv=128, nb=1, nq=9, nk=4096, nh=8, hd=16, scale=0.25, qr=None,
-                 kvr=None, kadd=None, io=1, O=p, ldo=128)
+                 kvr=None, kadd=None, O=p, ldo=128)
     fcall = lambda **kw: l.ink_attn_fewq(*{**fargs, **kw}.values(), None)
-    assert fcall(nq=17) == 1 and fcall(io=0) == 1 and fcall(nh=6) == 1
+    assert fcall(hd=32) == 1 and fcall(nh=6) == 1 and fcall(nh=2) == 1 and fcall(nq=17) == 1
+    # ink_attn_fewkeys: f16 rows exist for head_dim 32 and 64 only
+    kargs = dict(Q=p, ldq=128, K=p, ldk=128, V=p, ldv=128, B=1, nq=7, nk=7, nh=8, hd=16, scale=0.25, blocked=None,
+                 qr=None, qadd=None, io=0, O=p, ldo=128)
+    assert l.ink_attn_fewkeys(*kargs.values(), None) == 1
