@@ -342,6 +342,8 @@ int ink_biattn_fusion(const void* QV_f16, const void* KL_f16, int32_t B, int32_t
  * 1: f32 rows, hd in {16,32} (ld* in elements either way; the math is f32 in both).  q_batch_rows (int32 [B] or NULL):
  * first Q row of batch entry b (default b*n_q); keys and the output are dense.  q_add (f32 [n_q, n_heads*hd] or NULL) is
  * added to the query rows by position (the per-position constant pe.W of a projection of x + pe).
+ * Q, K, V, O and q_add must be 16-byte aligned and every ld* a multiple of 8 elements (the kernels move 16-byte vectors);
+ * anything else returns 1 with nothing launched.
  * Text self-attention (transformer_vanilla.py:114-116), decoder text cross-attention (transformer.py:893-900) and,
  * with f32 rows, the SAM mask decoder's token self-attention and image -> token attention
  * (SA/modeling/transformer.py:151-182: 7 x 7 and 4096 x 7). */
@@ -353,7 +355,9 @@ int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
 /* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
  * image: 7..16 x 4096, SA/modeling/transformer.py:163-168) on f32 rows: head h at columns [h*hd,(h+1)*hd), head_dim
  * must be 16 and n_heads a multiple of 4; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].
- * k_add (f32 [n_k, n_heads*hd] or NULL) is added to the key rows by key position. */
+ * k_add (f32 [n_k, n_heads*hd] or NULL) is added to the key rows by key position.
+ * Q, K, V, O and k_add must be 16-byte aligned and every ld* a multiple of 8 elements (the kernel moves 16-byte vectors);
+ * anything else returns 1 with nothing launched. */
 int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                   int32_t n_batch, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale,
                   const int32_t* q_batch_rows, const int32_t* kv_batch_rows, const float* k_add, void* O, int64_t ldo,

@@ -365,6 +365,8 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
   INK_CHECK_ARG(Q && K && V && O && B > 0 && n_q > 0 && n_k > 0 && n_k <= 16 && n_heads > 0);
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
   INK_CHECK_ARG(io_f32 == 0 || io_f32 == 1);
+  // every kernel moves 16-byte vectors: with ld % 8 == 0 an aligned base keeps every row aligned
+  INK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) == 0);
   INK_CHECK_ARG(!q_add || (((uintptr_t)q_add & 15) == 0));
   const int64_t total = (int64_t)B * n_q * n_heads;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
@@ -386,6 +388,7 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
     switch (n_k) {
       INK_FEWKEYS16(7); INK_FEWKEYS16(8); INK_FEWKEYS16(9); INK_FEWKEYS16(10); INK_FEWKEYS16(11);
       INK_FEWKEYS16(12); INK_FEWKEYS16(13); INK_FEWKEYS16(14); INK_FEWKEYS16(15); INK_FEWKEYS16(16);
+      default: return INK_ERR_ARG;                          // an n_k without an instantiation must not pass silently
     }
 #undef INK_FEWKEYS16
   } else if (head_dim == 16) INK_FEWKEYS(16, float);
@@ -401,6 +404,7 @@ extern "C" int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t 
   INK_CHECK_ARG(Q && K && V && O && n_batch > 0 && n_q > 0 && n_q <= 16 && n_k > 0 && n_heads > 0);
   INK_CHECK_ARG(head_dim == 16 && n_heads % 4 == 0);
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
+  INK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) == 0);   // 16-byte loads and stores
   INK_CHECK_ARG(!k_add || ((uintptr_t)k_add & 15) == 0);
   // two key-range groups x (K, V) tiles of 64 keys x 4 heads x 16 f32; at 4 queries per wave also the scaled queries
   constexpr int lds2 = 2 * 2 * 64 * 64 * 4, lds4 = lds2 + 16 * 64 * 4;

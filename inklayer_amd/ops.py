@@ -950,6 +950,7 @@ def attn_fewkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n
     io = q.dtype
     for t in (q, k, v):
         assert t.dtype == io and io in (F16, F32) and t.dim() == 2 and t.stride(1) == 1
+        assert t.data_ptr() % 16 == 0                      # 16-byte vector loads (the row strides: ld % 8 in the C entry)
     if n_q is None:
         n_q = q.shape[0] // B
     n_k = k.shape[0] // B
@@ -974,6 +975,9 @@ def attn_fewq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: int
     flash_attn."""
     for t in (q, k, v):
         assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1
+        assert t.data_ptr() % 16 == 0                      # 16-byte vector loads (the row strides: ld % 8 in the C entry)
+    for rows in (q_batch_rows, kv_batch_rows):
+        assert rows is None or (rows.dtype == torch.int32 and rows.numel() == n_batch and rows.is_cuda)
     out = torch.empty((n_batch * n_q, n_heads * head_dim), device=q.device, dtype=F32)
     if k_add is not None:
         assert k_add.dtype == F32 and k_add.is_contiguous() and tuple(k_add.shape) == (n_k, n_heads * head_dim)

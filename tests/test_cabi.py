@@ -49,6 +49,61 @@ def test_bad_arguments_are_rejected_without_launch():
     assert l.ink_add_split_f16(16, None, 0, 16, 8, 3, None) == 1            # C % 4 != 0
 
 
+def test_attn_fewkeys_argument_contract():
+    """ink_attn_fewkeys returns 1 before any launch for every form it has no kernel for and for rows or pointers its
+    16-byte vector loads and stores cannot take.  Fake non-null pointers: none of these calls may be accepted."""
+    from inklayer_amd import _lib
+    l = _lib.lib()
+    p = 16
+    args = dict(Q=p, ldq=128, K=p, ldk=128, V=p, ldv=128, B=1, nq=7, nk=7, nh=8, hd=16, scale=0.25, blocked=None,
+                qr=None, qadd=None, io=1, O=p, ldo=128)
+    call = lambda **kw: l.ink_attn_fewkeys(*{**args, **kw}.values(), None)
+    assert call(nk=17) == 1 and call(nk=0) == 1
+    assert call(hd=16, io=0) == 1                       # f16 rows: head_dim 32 and 64 only
+    assert call(hd=48) == 1 and call(hd=48, io=0) == 1 and call(hd=64) == 1      # f32 rows: 16 and 32 only
+    assert call(io=2) == 1 and call(io=-1) == 1
+    assert call(ldq=12) == 1 and call(ldk=132) == 1 and call(ldv=4) == 1 and call(ldo=129) == 1
+    assert call(Q=8) == 1 and call(K=24) == 1 and call(V=20) == 1 and call(O=40) == 1
+    assert call(qadd=24) == 1 and call(qadd=4) == 1
+    assert call(Q=None) == 1 and call(O=None) == 1
+
+
+def test_attn_fewq_argument_contract():
+    """The same for ink_attn_fewq: f32 rows, head_dim 16, n_heads % 4 == 0, n_q <= 16, aligned rows and pointers."""
+    from inklayer_amd import _lib
+    l = _lib.lib()
+    p = 16
+    args = dict(Q=p, ldq=128, K=p, ldk=128, V=p, ldv=128, nb=1, nq=9, nk=4096, nh=8, hd=16, scale=0.25, qr=None,
+                kvr=None, kadd=None, O=p, ldo=128)
+    call = lambda **kw: l.ink_attn_fewq(*{**args, **kw}.values(), None)
+    assert call(nq=17) == 1 and call(nq=0) == 1 and call(nk=0) == 1
+    assert call(hd=32) == 1 and call(nh=6) == 1
+    assert call(ldk=4) == 1 and call(ldq=12) == 1 and call(ldv=130) == 1 and call(ldo=60) == 1
+    assert call(K=24) == 1 and call(Q=8) == 1 and call(V=4) == 1 and call(O=72) == 1
+    assert call(kadd=24) == 1 and call(kadd=8) == 1
+    assert call(K=None) == 1
+
+
+def test_attn_few_wrappers_refuse_misaligned_rows():
+    """ops.attn_fewkeys / ops.attn_fewq assert 16-byte aligned q, k, v before anything native is called (CPU tensors: a
+    view that starts 8 bytes into a row)."""
+    import pytest
+    import torch
+    from inklayer_amd import ops
+    for dtype, col in ((torch.float32, 2), (torch.float16, 4)):
+        good = torch.zeros(14, 256, dtype=dtype)
+        bad = torch.zeros(14, 272, dtype=dtype)[:, col:col + 256]
+        assert good.data_ptr() % 16 == 0 and bad.data_ptr() % 16 == 8 and bad.stride(1) == 1
+        for i in range(3):
+            qkv = [good, good, good]
+            qkv[i] = bad
+            with pytest.raises(AssertionError):
+                ops.attn_fewkeys(*qkv, B=2, n_heads=8, head_dim=32, scale=0.25)
+            if dtype == torch.float32:
+                with pytest.raises(AssertionError):
+                    ops.attn_fewq(*qkv, n_batch=2, n_heads=16, head_dim=16, scale=0.25, n_q=7, n_k=7)
+
+
 def test_gemm_variant_hook_accepts_only_shipped_tile_families():
     """VERDICT r1 / ADVICE: the library ships only the GEMM tile families the shape heuristic dispatches, and the test
     hook ink_gemm_set_variant accepts exactly those (-1 = the heuristic): no sweep tiling, no persistent or
