@@ -491,69 +491,78 @@ class GDinoEngine:
 
     def encoder(self, src: torch.Tensor, pl: _Plan, B: int):
         """TransformerEncoder.forward (transformer.py:481-595): fusion -> text layer -> deformable layer, x6."""
-        cfg, w, dev, T, S = self.cfg, self.w, self.dev, self.T, pl.S
+        S = pl.S
         text = self.text0.repeat(B, 1)                        # [B*T, 256] (plumbing copy)
-        s16 = torch.empty((B * S, 256), device=dev, dtype=F16)
-        s16p = torch.empty((B * S, 256), device=dev, dtype=F16)
-        for i in range(cfg.enc_layers):
-            d = f"e{i}"
-            have16 = False
-            # --- BiAttentionBlock (fuse_modules.py:286-295): residual from the NORMALISED v / l
-            ln32 = torch.empty_like(text)
-            l16 = torch.empty(text.shape, device=dev, dtype=F16)
-            ops.layernorm_rows(text, w[d + ".fu.lnl.w"], w[d + ".fu.lnl.b"], 1e-5, out=ln32, out2=l16)
-            if self.fold_fusion and T <= 4:
-                # the caption's <= 4 tokens folded through the fusion layer (csrc/fusion_fold.hip): no per-token
-                # 256 -> 2048 projection, no 1024 -> 256 image output projection, f32 throughout
-                kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"])
-                # ... and the f16 operands of this layer's deformable attention (x + pos, x) leave in the same pass
-                ol = ops.fusion_fold(src, B, S, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, kl, T, w[d + ".fu.qv.w"],
-                                     w[d + ".fu.qv.b"], w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], w[d + ".fu.gv"],
-                                     256 ** -0.5, pos=pl.pos, out16_pos=s16p, out16=s16)
-                have16 = True
-            else:
-                vn = torch.empty_like(src)
-                ops.layernorm_rows(src, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, out=vn, out2=s16)
-                qv = ops.gemm(s16, w[d + ".fu.qv.w"], w[d + ".fu.qv.b"], out_dtype=F16)
-                kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"], out_dtype=F16)
-                ov, ol = ops.biattn_fusion(qv, kl, B, S, T, 256 ** -0.5)
-                src = ops.gemm(ov, w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], col_scale=w[d + ".fu.gv"], residual=vn, out=vn)
-            text = ops.gemm(ol, w[d + ".fu.outl.w"], w[d + ".fu.outl.b"], col_scale=w[d + ".fu.gl"], residual=ln32)
-            # --- text enhancer (transformer_vanilla.py:101-123), 4 heads x 64, block-diagonal mask
-            qk = ops.gemm(ops.add_cvt_f16(text, self.pos_text), w[d + ".txt.qk.w"], w[d + ".txt.qk.b"], out_dtype=F16)
-            vv = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.v.w"], w[d + ".txt.v.b"], out_dtype=F16)
-            a = ops.attn_fewkeys(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
-                                 blocked=self.text_blocked)
-            text = ops.layernorm_rows(ops.gemm(a, w[d + ".txt.out.w"], w[d + ".txt.out.b"], residual=text),
-                                      w[d + ".txt.norm1.w"], w[d + ".txt.norm1.b"], 1e-5, out_dtype=F32)
-            ff = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.lin1.w"], w[d + ".txt.lin1.b"], act="relu", out_dtype=F16)
-            text = ops.layernorm_rows(ops.gemm(ff, w[d + ".txt.lin2.w"], w[d + ".txt.lin2.b"], residual=text),
-                                      w[d + ".txt.norm2.w"], w[d + ".txt.norm2.b"], 1e-5, out_dtype=F32)
-            # --- DeformableTransformerEncoderLayer (transformer.py:780-799)
-            if have16:
-                proj = ops.gemm(s16p, w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
-                val = ops.gemm(s16, w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
-            else:
-                proj = ops.gemm(ops.add_cvt_f16(src, pl.pos, out=s16), w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
-                val = ops.gemm(ops.add_cvt_f16(src, out=s16), w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
-            o = ops.msda_fused(val, proj, pl.enc_ref, pl.shapes, B, S, ref_batched=False)
-            if self.fuse_ffn and self.fuse_ffn_pre and (d + ".ffn.blob_pre") in w:
-                # out_proj + residual + norm1 + linear1 + relu + linear2 + residual + norm2: one kernel, `src` read and
-                # written once
-                ops.ffn256_fused(o, src, w[d + ".ffn.blob_pre"], int(w[d + ".lin1.b"].numel()), w[d + ".lin2.b"],
-                                 w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src,
-                                 pre=(w[d + ".msda.out.b"], w[d + ".norm1.w"], w[d + ".norm1.b"]))
-                continue
-            y = ops.gemm(o, w[d + ".msda.out.w"], w[d + ".msda.out.b"], residual=src, out=src)
-            ops.layernorm_rows(y, w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, out=src, out2=s16)
-            if self.fuse_ffn and (d + ".ffn.blob") in w:
-                # linear1 + relu + linear2 + residual + norm2 in one kernel: the [B*S, 2048] hidden tensor stays in registers
-                ops.ffn256_fused(s16, src, w[d + ".ffn.blob"], int(w[d + ".lin1.b"].numel()), w[d + ".lin2.b"],
-                                 w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src)
-            else:
-                ff = ops.gemm(s16, w[d + ".lin1.w"], w[d + ".lin1.b"], act="relu", out_dtype=F16)
-                y = ops.gemm(ff, w[d + ".lin2.w"], w[d + ".lin2.b"], residual=src, out=src)
-                ops.layernorm_rows(y, w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src)
+        s16 = torch.empty((B * S, 256), device=self.dev, dtype=F16)
+        s16p = torch.empty((B * S, 256), device=self.dev, dtype=F16)
+        for i in range(self.cfg.enc_layers):
+            src, text = self._enc_layer(i, src, text, pl, B, s16, s16p)
+        return src, text
+
+    def _enc_layer(self, i: int, src: torch.Tensor, text: torch.Tensor, pl: _Plan, B: int, s16: torch.Tensor,
+                   s16p: torch.Tensor):
+        """Encoder layer i: fusion, text enhancer, deformable layer on src [B*S, 256] f32 (updated in place on the
+        product path) and text [B*T, 256] f32; s16 / s16p are the [B*S, 256] f16 operand buffers every layer re-uses.
+        Returns (src, text)."""
+        w, dev, T, S = self.w, self.dev, self.T, pl.S
+        d = f"e{i}"
+        have16 = False
+        # --- BiAttentionBlock (fuse_modules.py:286-295): residual from the NORMALISED v / l
+        ln32 = torch.empty_like(text)
+        l16 = torch.empty(text.shape, device=dev, dtype=F16)
+        ops.layernorm_rows(text, w[d + ".fu.lnl.w"], w[d + ".fu.lnl.b"], 1e-5, out=ln32, out2=l16)
+        if self.fold_fusion and T <= 4:
+            # the caption's <= 4 tokens folded through the fusion layer (csrc/fusion_fold.hip): no per-token
+            # 256 -> 2048 projection, no 1024 -> 256 image output projection, f32 throughout
+            kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"])
+            # ... and the f16 operands of this layer's deformable attention (x + pos, x) leave in the same pass
+            ol = ops.fusion_fold(src, B, S, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, kl, T, w[d + ".fu.qv.w"],
+                                 w[d + ".fu.qv.b"], w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], w[d + ".fu.gv"],
+                                 256 ** -0.5, pos=pl.pos, out16_pos=s16p, out16=s16)
+            have16 = True
+        else:
+            vn = torch.empty_like(src)
+            ops.layernorm_rows(src, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, out=vn, out2=s16)
+            qv = ops.gemm(s16, w[d + ".fu.qv.w"], w[d + ".fu.qv.b"], out_dtype=F16)
+            kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"], out_dtype=F16)
+            ov, ol = ops.biattn_fusion(qv, kl, B, S, T, 256 ** -0.5)
+            src = ops.gemm(ov, w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], col_scale=w[d + ".fu.gv"], residual=vn, out=vn)
+        text = ops.gemm(ol, w[d + ".fu.outl.w"], w[d + ".fu.outl.b"], col_scale=w[d + ".fu.gl"], residual=ln32)
+        # --- text enhancer (transformer_vanilla.py:101-123), 4 heads x 64, block-diagonal mask
+        qk = ops.gemm(ops.add_cvt_f16(text, self.pos_text), w[d + ".txt.qk.w"], w[d + ".txt.qk.b"], out_dtype=F16)
+        vv = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.v.w"], w[d + ".txt.v.b"], out_dtype=F16)
+        a = ops.attn_fewkeys(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
+                             blocked=self.text_blocked)
+        text = ops.layernorm_rows(ops.gemm(a, w[d + ".txt.out.w"], w[d + ".txt.out.b"], residual=text),
+                                  w[d + ".txt.norm1.w"], w[d + ".txt.norm1.b"], 1e-5, out_dtype=F32)
+        ff = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.lin1.w"], w[d + ".txt.lin1.b"], act="relu", out_dtype=F16)
+        text = ops.layernorm_rows(ops.gemm(ff, w[d + ".txt.lin2.w"], w[d + ".txt.lin2.b"], residual=text),
+                                  w[d + ".txt.norm2.w"], w[d + ".txt.norm2.b"], 1e-5, out_dtype=F32)
+        # --- DeformableTransformerEncoderLayer (transformer.py:780-799)
+        if have16:
+            proj = ops.gemm(s16p, w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
+            val = ops.gemm(s16, w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
+        else:
+            proj = ops.gemm(ops.add_cvt_f16(src, pl.pos, out=s16), w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
+            val = ops.gemm(ops.add_cvt_f16(src, out=s16), w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
+        o = ops.msda_fused(val, proj, pl.enc_ref, pl.shapes, B, S, ref_batched=False)
+        if self.fuse_ffn and self.fuse_ffn_pre and (d + ".ffn.blob_pre") in w:
+            # out_proj + residual + norm1 + linear1 + relu + linear2 + residual + norm2: one kernel, `src` read and
+            # written once
+            ops.ffn256_fused(o, src, w[d + ".ffn.blob_pre"], int(w[d + ".lin1.b"].numel()), w[d + ".lin2.b"],
+                             w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src,
+                             pre=(w[d + ".msda.out.b"], w[d + ".norm1.w"], w[d + ".norm1.b"]))
+            return src, text
+        y = ops.gemm(o, w[d + ".msda.out.w"], w[d + ".msda.out.b"], residual=src, out=src)
+        ops.layernorm_rows(y, w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, out=src, out2=s16)
+        if self.fuse_ffn and (d + ".ffn.blob") in w:
+            # linear1 + relu + linear2 + residual + norm2 in one kernel: the [B*S, 2048] hidden tensor stays in registers
+            ops.ffn256_fused(s16, src, w[d + ".ffn.blob"], int(w[d + ".lin1.b"].numel()), w[d + ".lin2.b"],
+                             w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src)
+        else:
+            ff = ops.gemm(s16, w[d + ".lin1.w"], w[d + ".lin1.b"], act="relu", out_dtype=F16)
+            y = ops.gemm(ff, w[d + ".lin2.w"], w[d + ".lin2.b"], residual=src, out=src)
+            ops.layernorm_rows(y, w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out=src)
         return src, text
 
     def decoder(self, memory: torch.Tensor, text: torch.Tensor, pl: _Plan, B: int, stages: Optional[dict] = None):
@@ -582,41 +591,59 @@ class GDinoEngine:
         output = w["tgt"].repeat(B, 1)                       # embed_init_tgt (transformer.py:318-321)
         mem16 = ops.add_cvt_f16(memory)
         hs16 = None
+        if stages is not None:
+            stages["hs"], stages["refs"] = [], [ref.clone()]
         for i in range(cfg.dec_layers):
-            d = f"d{i}"
-            qse = ops.sine_embed4(ref, w["dim_t"])
-            qpos = ops.gemm(ops.gemm(qse, w["rph0.w"], w["rph0.b"], act="relu", out_dtype=F16), w["rph1.w"], w["rph1.b"])
-            # self-attention over the 900 queries
-            qk = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".sa.qk.w"], w[d + ".sa.qk.b"], out_dtype=F16)
-            vv = ops.gemm(ops.add_cvt_f16(output), w[d + ".sa.v.w"], w[d + ".sa.v.b"], out_dtype=F16)
-            a = ops.flash_attn(qk[:, :256], qk[:, 256:], vv, n_batch=B, n_heads=8, head_dim=32, scale=32 ** -0.5,
-                               n_q=nq, n_k=nq)
-            output = ops.layernorm_rows(ops.gemm(a, w[d + ".sa.out.w"], w[d + ".sa.out.b"], residual=output),
-                                        w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out_dtype=F32)
-            # text cross-attention (keys/values = the T text tokens)
-            q = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".ca.q.w"], w[d + ".ca.q.b"], out_dtype=F16)
-            kv = ops.gemm(text16, w[d + ".ca.kv.w"], w[d + ".ca.kv.b"], out_dtype=F16)
-            a = ops.attn_fewkeys(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
-            output = ops.layernorm_rows(ops.gemm(a, w[d + ".ca.out.w"], w[d + ".ca.out.b"], residual=output),
-                                        w[d + ".canorm.w"], w[d + ".canorm.b"], 1e-5, out_dtype=F32)
-            # deformable cross-attention into the encoder memory (4-d reference boxes)
-            proj = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
-            val = ops.gemm(mem16, w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
-            o = ops.msda_fused(val, proj, ref, pl.shapes, B, nq, ref_batched=True)
-            output = ops.layernorm_rows(ops.gemm(o, w[d + ".msda.out.w"], w[d + ".msda.out.b"], residual=output),
-                                        w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, out_dtype=F32)
-            ff = ops.gemm(ops.add_cvt_f16(output), w[d + ".lin1.w"], w[d + ".lin1.b"], act="relu", out_dtype=F16)
-            output = ops.layernorm_rows(ops.gemm(ff, w[d + ".lin2.w"], w[d + ".lin2.b"], residual=output),
-                                        w[d + ".norm3.w"], w[d + ".norm3.b"], 1e-5, out_dtype=F32)
+            output = self._dec_layer(i, output, ref, mem16, text16, pl, B)
+            if stages is not None:                           # BEFORE dec.norm (the oracle's stages["hs"] are after it)
+                stages["hs"].append(output.clone())
             if i < cfg.dec_layers - 1:
                 ref = ops.box_refine(self._mlp3("box", ops.add_cvt_f16(output)), ref)
+                if stages is not None:
+                    stages["refs"].append(ref.clone())
             else:
+                if stages is not None:                       # the oracle's refs[-1]: refined, never used
+                    stages["refs"].append(ops.box_refine(self._mlp3("box", ops.add_cvt_f16(output)), ref))
                 hs16 = ops.layernorm_rows(output, w["dec.norm.w"], w["dec.norm.b"], 1e-5)
         boxes = ops.box_refine(self._mlp3("box", hs16), ref).view(B, nq, 4)
         out_logits = torch.empty((B, nq, T), device=dev, dtype=F32)
         for b in range(B):
             ops.gemm(hs16[b * nq:(b + 1) * nq], text16[b * T:(b + 1) * T], out=out_logits[b])
         return out_logits, boxes
+
+    def _dec_layer(self, i: int, output: torch.Tensor, ref: torch.Tensor, mem16: torch.Tensor, text16: torch.Tensor,
+                   pl: _Plan, B: int) -> torch.Tensor:
+        """Decoder layer i (transformer.py:868-927) on the f32 queries output [B*nq, 256] with the sigmoided reference
+        boxes ref [B*nq, 4], the f16 encoder memory [B*S, 256] and the f16 text rows [B*T, 256].  Returns the new
+        f32 output (before decoder.norm and the box refinement)."""
+        w = self.w
+        nq = output.shape[0] // B
+        d = f"d{i}"
+        qse = ops.sine_embed4(ref, w["dim_t"])
+        qpos = ops.gemm(ops.gemm(qse, w["rph0.w"], w["rph0.b"], act="relu", out_dtype=F16), w["rph1.w"], w["rph1.b"])
+        # self-attention over the 900 queries
+        qk = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".sa.qk.w"], w[d + ".sa.qk.b"], out_dtype=F16)
+        vv = ops.gemm(ops.add_cvt_f16(output), w[d + ".sa.v.w"], w[d + ".sa.v.b"], out_dtype=F16)
+        a = ops.flash_attn(qk[:, :256], qk[:, 256:], vv, n_batch=B, n_heads=8, head_dim=32, scale=32 ** -0.5,
+                           n_q=nq, n_k=nq)
+        output = ops.layernorm_rows(ops.gemm(a, w[d + ".sa.out.w"], w[d + ".sa.out.b"], residual=output),
+                                    w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5, out_dtype=F32)
+        # text cross-attention (keys/values = the T text tokens)
+        q = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".ca.q.w"], w[d + ".ca.q.b"], out_dtype=F16)
+        kv = ops.gemm(text16, w[d + ".ca.kv.w"], w[d + ".ca.kv.b"], out_dtype=F16)
+        a = ops.attn_fewkeys(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
+        output = ops.layernorm_rows(ops.gemm(a, w[d + ".ca.out.w"], w[d + ".ca.out.b"], residual=output),
+                                    w[d + ".canorm.w"], w[d + ".canorm.b"], 1e-5, out_dtype=F32)
+        # deformable cross-attention into the encoder memory (4-d reference boxes)
+        proj = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".msda.proj.w"], w[d + ".msda.proj.b"])
+        val = ops.gemm(mem16, w[d + ".msda.value.w"], w[d + ".msda.value.b"], out_dtype=F16)
+        o = ops.msda_fused(val, proj, ref, pl.shapes, B, nq, ref_batched=True)
+        output = ops.layernorm_rows(ops.gemm(o, w[d + ".msda.out.w"], w[d + ".msda.out.b"], residual=output),
+                                    w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, out_dtype=F32)
+        ff = ops.gemm(ops.add_cvt_f16(output), w[d + ".lin1.w"], w[d + ".lin1.b"], act="relu", out_dtype=F16)
+        output = ops.layernorm_rows(ops.gemm(ff, w[d + ".lin2.w"], w[d + ".lin2.b"], residual=output),
+                                    w[d + ".norm3.w"], w[d + ".norm3.b"], 1e-5, out_dtype=F32)
+        return output
 
     # ------------------------------------------------------------------ whole model
     def forward(self, images_u8: Sequence[torch.Tensor], stages: Optional[dict] = None, allow_graph: bool = True):

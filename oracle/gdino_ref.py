@@ -362,7 +362,7 @@ def msda_core(value: torch.Tensor, shapes: Sequence[Tuple[int, int]], loc: torch
     and out-of-range corners contribute 0 (== grid_sample(zeros, align_corners=False))."""
     B, S, M, C = value.shape
     Q, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
-    out = torch.zeros(B, Q, M, C, dtype=value.dtype)
+    out = torch.zeros(B, Q, M, C, dtype=value.dtype, device=value.device)
     start = 0
     for l, (H, W) in enumerate(shapes):
         v = value[:, start:start + H * W].permute(0, 2, 1, 3)          # B,M,HW,C
@@ -371,7 +371,7 @@ def msda_core(value: torch.Tensor, shapes: Sequence[Tuple[int, int]], loc: torch
         x0, y0 = torch.floor(x), torch.floor(y)
         lx, ly = x - x0, y - y0
         inside = (y > -1) & (x > -1) & (y < H) & (x < W)
-        acc = torch.zeros(B, Q, M, P, C, dtype=value.dtype)
+        acc = torch.zeros(B, Q, M, P, C, dtype=value.dtype, device=value.device)
         for dy, dx, wt in ((0, 0, (1 - ly) * (1 - lx)), (0, 1, (1 - ly) * lx),
                            (1, 0, ly * (1 - lx)), (1, 1, ly * lx)):
             yy, xx = (y0 + dy).long(), (x0 + dx).long()
@@ -518,6 +518,48 @@ def encoder_proposals(shapes: Sequence[Tuple[int, int]]):
     return pr, valid
 
 
+def two_stage_selection(sd: SD, cfg: GDinoConfig, memory: torch.Tensor, text: torch.Tensor,
+                        shapes: Sequence[Tuple[int, int]], force_topk: torch.Tensor | None = None):
+    """Two-stage query selection (transformer.py:284-327): memory [B,S,D], text [B,T,D] ->
+    (order [B,nq] token indices, logits [B,S] max over the text tokens, ref_unsig [B,nq,4] unsigmoided boxes).
+    force_topk pins the selection (test hook: sensitivity probes, per-query comparisons)."""
+    t = "transformer."
+    props, valid = encoder_proposals(shapes)
+    props, valid = props.to(memory.device), valid.to(memory.device)
+    om = memory.masked_fill(~valid[None, :, None], 0.0)
+    om = _ln(F.linear(om, sd[t + "enc_output.weight"], sd[t + "enc_output.bias"]), sd, t + "enc_output_norm")
+    logits = (om @ text.transpose(-1, -2)).max(-1)[0]                                       # B,S
+    coord_unsel = mlp(sd, t + "enc_out_bbox_embed.", om, 3) + props[None]
+    # top-k by value, ties -> lower index first (torch.topk's tie order is unspecified)
+    order = torch.sort(logits, dim=1, descending=True, stable=True)[1][:, :cfg.num_queries]
+    if force_topk is not None:
+        order = force_topk.long()
+    ref_unsig = torch.gather(coord_unsel, 1, order[..., None].expand(-1, -1, 4))
+    return order, logits, ref_unsig
+
+
+def decoder_layer(sd: SD, cfg: GDinoConfig, i: int, output: torch.Tensor, ref: torch.Tensor, text: torch.Tensor,
+                  memory: torch.Tensor, shapes: Sequence[Tuple[int, int]]):
+    """Layer i of TransformerDecoder.forward + DeformableTransformerDecoderLayer.forward (transformer.py:665-735,
+    868-927) with the shared box head's refinement: output [B,nq,D], ref [B,nq,4] sigmoided boxes, text [B,T,D],
+    memory [B,S,D] -> (output before decoder.norm, new_ref)."""
+    t = "transformer."
+    p = f"{t}decoder.layers.{i}."
+    ref_in = ref[:, :, None, :].expand(-1, -1, cfg.num_feature_levels, -1)           # valid_ratios == 1
+    qse = sine_embed_4d(ref_in[:, :, 0, :])
+    qpos = mlp(sd, t + "decoder.ref_point_head.", qse, 2)
+    q = output + qpos
+    output = _ln(output + mha(sd, p + "self_attn.", q, q, output, cfg.nheads), sd, p + "norm2")
+    output = _ln(output + mha(sd, p + "ca_text.", output + qpos, text, text, cfg.nheads), sd, p + "catext_norm")
+    output = _ln(output + msda_module(sd, p + "cross_attn.", cfg, output + qpos, ref_in, memory, shapes),
+                 sd, p + "norm1")
+    f = F.linear(F.relu(F.linear(output, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
+                 sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+    output = _ln(output + f, sd, p + "norm3")
+    new_ref = (mlp(sd, "bbox_embed.0.", output, 3) + inverse_sigmoid(ref)).sigmoid()
+    return output, new_ref
+
+
 # ----------------------------------------------------------------------------------------
 # whole detector
 # ----------------------------------------------------------------------------------------
@@ -559,16 +601,8 @@ def detector_forward(sd: SD, cfg: GDinoConfig, img: torch.Tensor, encoded_text: 
     if stages is not None:
         stages["memory"], stages["memory_text"] = memory.clone(), text.clone()
     # ---- two-stage query selection (transformer.py:284-327)
-    props, valid = encoder_proposals(shapes)
-    om = memory.masked_fill(~valid[None, :, None], 0.0)
-    om = _ln(F.linear(om, sd[t + "enc_output.weight"], sd[t + "enc_output.bias"]), sd, t + "enc_output_norm")
-    logits = (om @ text.transpose(-1, -2)).max(-1)[0]                                       # B,S
-    coord_unsel = mlp(sd, t + "enc_out_bbox_embed.", om, 3) + props[None]
-    # top-k by value, ties -> lower index first (torch.topk's tie order is unspecified)
-    order = torch.sort(logits, dim=1, descending=True, stable=True)[1][:, :cfg.num_queries]
-    if stages is not None and "force_topk" in stages:     # test hook: pin the query selection (sensitivity probes)
-        order = stages["force_topk"].long()
-    ref_unsig = torch.gather(coord_unsel, 1, order[..., None].expand(-1, -1, 4))
+    force = stages["force_topk"] if stages is not None and "force_topk" in stages else None
+    order, logits, ref_unsig = two_stage_selection(sd, cfg, memory, text, shapes, force)
     tgt = sd[t + "tgt_embed.weight"][None].expand(B, -1, -1)
     if stages is not None:
         stages["topk"], stages["topk_logits"], stages["ref_unsig"] = order.clone(), logits.clone(), ref_unsig.clone()
@@ -577,19 +611,7 @@ def detector_forward(sd: SD, cfg: GDinoConfig, img: torch.Tensor, encoded_text: 
     output = tgt
     hs, refs = [], [ref]
     for i in range(cfg.dec_layers):
-        p = f"{t}decoder.layers.{i}."
-        ref_in = ref[:, :, None, :].expand(-1, -1, cfg.num_feature_levels, -1)           # valid_ratios == 1
-        qse = sine_embed_4d(ref_in[:, :, 0, :])
-        qpos = mlp(sd, t + "decoder.ref_point_head.", qse, 2)
-        q = output + qpos
-        output = _ln(output + mha(sd, p + "self_attn.", q, q, output, cfg.nheads), sd, p + "norm2")
-        output = _ln(output + mha(sd, p + "ca_text.", output + qpos, text, text, cfg.nheads), sd, p + "catext_norm")
-        output = _ln(output + msda_module(sd, p + "cross_attn.", cfg, output + qpos, ref_in, memory, shapes),
-                     sd, p + "norm1")
-        f = F.linear(F.relu(F.linear(output, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
-                     sd[p + "linear2.weight"], sd[p + "linear2.bias"])
-        output = _ln(output + f, sd, p + "norm3")
-        ref = (mlp(sd, "bbox_embed.0.", output, 3) + inverse_sigmoid(ref)).sigmoid()
+        output, ref = decoder_layer(sd, cfg, i, output, ref, text, memory, shapes)
         refs.append(ref)
         hs.append(_ln(output, sd, t + "decoder.norm"))
     # ---- heads (groundingdino.py:331-349): last layer only

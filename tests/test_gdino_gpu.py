@@ -163,9 +163,12 @@ def test_detector_stages_match_oracle(dev, small_dino):
     assert len(got & want) >= 0.97 * 300
     mx, l2 = _rel(est["ref0"], st["refs"][0][0])
     assert mx < 1e-2
-    # decoder outputs per query: with RANDOM weights ~10 % of the queries are ill-conditioned (large random
-    # sampling offsets on a random feature map; even two fp32 runs differ by 1e-3 there, see
-    # tests/test_oracle_gdino.py), so the median / 75th percentile are held tight and the tail loose.
+    # decoder outputs per query: with RANDOM weights ~10 % of the queries are ill-conditioned (the seeded q / k
+    # projections make the 900-query self-attention an argmax - score std ~330, median max-probability 1.000 - so a
+    # rounding that changes the winning key moves the query by O(1); scaling the sampling-offset projections down changes
+    # nothing, tests/detector_layers_ref.py; even two fp32 runs differ by 1e-3 there, see tests/test_oracle_gdino.py), so
+    # the median / 75th percentile are held tight and the tail loose.  tests/test_detector_layers_gpu.py holds the same
+    # layers on well-conditioned weights with no loose tail.
     d = (boxes[0].cpu() - ref_boxes[0]).abs().max(-1)[0]
     print("box err p50/p75/p90/max", d.median().item(), d.quantile(0.75).item(), d.quantile(0.9).item(), d.max().item())
     assert d.median().item() < 1e-3 and d.quantile(0.75).item() < 3e-3 and d.quantile(0.9).item() < 2e-2
@@ -175,8 +178,8 @@ def test_detector_stages_match_oracle(dev, small_dino):
     # MAX bound, justified by the oracle's OWN sensitivity to the stated arithmetic: the fp32 oracle is re-run with the
     # operands of every linear / conv rounded to f16 (exactly what DESIGN.md §4 says the HIP path does; weights and
     # activations, f32 accumulation) and, separately, with f16 weights only, with the query selection pinned.  With
-    # RANDOM weights ~10 % of the queries are ill-conditioned (large random sampling offsets on a random feature map)
-    # and move by up to several 1e-2 under that rounding in the fp32 oracle itself.  So
+    # RANDOM weights ~10 % of the queries are ill-conditioned (the saturated self-attention of the seeded weights, see
+    # above) and move by up to several 1e-2 under that rounding in the fp32 oracle itself.  So
     #   (1) every quantile of the HIP error INCLUDING THE MAXIMUM is bounded by 2x the emulated-f16 oracle's, and
     #   (2) per query: err(q) <= 2e-3 + 20 * sens(q), sens = the query's own movement under the probes, for all but
     #       2 % of the queries (a different rounding realisation can hit a query the probes happened to miss).
