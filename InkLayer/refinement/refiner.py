@@ -115,6 +115,7 @@ def run_refinement_on_sketch_dir(sketch_dir, bboxes_path, out_base_dir=None, cle
     shutil.rmtree(out_dir, ignore_errors=True)
     os.makedirs(out_dir, exist_ok=True)
     final_masks = res.final_masks()
+    run_refinement_on_sketch_dir.last_final_masks = (os.path.abspath(sketch_dir), final_masks)   # for the layer stage
     save_all((((np.asarray(m) > 0).astype(np.uint8) * 255, f"{out_dir}/mask_{i}.png") for i, m in enumerate(final_masks)), wait=None)
     depth_map = depth_dev.cpu().numpy()
     lo, hi = float(depth_map.min()), float(depth_map.max())             # cv2.normalize(NORM_MINMAX, 0..255)

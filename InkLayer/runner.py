@@ -2,7 +2,9 @@
 for the detector -> segmentor part:  <out_base_dir>/<name>/{input.png, bboxes.json, masks/mask_i.png,
 segmented_sketch.png, bboxes.png, masks_cleaned/, bboxes_final.json, bboxes_final.png, masks_disjoint/, masks_final/,
 depth_map.png, segmented_sketch_final.png}.  Detector, segmentor, mask cleanup, sketch-NMS pair table and the depth model
-run on the GPU; inpainting (diffusers) is outside this build's scope and is skipped with a message."""
+run on the GPU; so does the layer assembly around the inpainting model (complete_layers/, complete_layers_process/,
+complete_layers_rgba/) once a model function is registered with InkLayer.inpainting.set_inpaint_func - the diffusion model
+itself is not part of this build, and without a function the step is skipped with a message."""
 import os
 import shutil
 
@@ -120,7 +122,22 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
         from InkLayer.refinement.refiner import run_refinement_on_sketch_dir
         run_refinement_on_sketch_dir(out_dir, bbox_out_path, cleaned_masks=cleaned, sketch_rgb=rgb)
         _tick("depth + refinement stage + masks_disjoint/ masks_final/ (files)", t0)
-        if inpaint:
+        import InkLayer.inpainting as _inp
+        if inpaint and _inp.get_inpaint_func() is not None:
+            # Layer assembly (runner.py:79-84) around the registered inpainting function, from the final masks the
+            # refinement stage just produced (not re-read from masks_final/, whose files may still be in the I/O queue)
+            t0 = time.perf_counter()
+            from InkLayer.inpainting.util import write_layers
+            from InkLayer.inpainting.fill_object_bg_mask import rgba_layers_to_dir
+            held_dir, final_masks = getattr(run_refinement_on_sketch_dir, "last_final_masks", (None, None))
+            assert held_dir == os.path.abspath(out_dir), "the refinement stage did not leave this sketch's final masks"
+            masks_u8 = np.stack([(np.asarray(m) > 0).astype(np.uint8) * 255 for m in final_masks]) if len(final_masks) \
+                else np.zeros((0,) + rgb.shape[:2], np.uint8)
+            inpainted_dir, layer_pixels = write_layers(out_dir, rgb, masks_u8, _inp.get_inpaint_func())
+            print(f"Inpainting completed. Output saved to {inpainted_dir}")
+            rgba_layers_to_dir(layer_pixels, inpainted_dir.replace("layers", "layers_rgba"))
+            _tick("layer assembly + inpainting function + RGBA layers (GPU + files)", t0)
+        elif inpaint:
             print("Inpainting (diffusers) is not part of this build: skipped.")
         else:
             print("Skipping inpainting step as 'inpaint' is set to False.")
@@ -152,4 +169,25 @@ def run_inklayer_pipeline(input_path, out_base_dir, no_intermediate=False, inpai
 
 
 def run_inpaint_single_layer(request_data, cur_dir, out_dir):
-    raise NotImplementedError("layer inpainting (InkLayer/inpainting, diffusers) is outside this build's scope")
+    """runner.py:104-172: the layer's mask grown to its box + 10 px, handed to the registered inpainting function."""
+    import InkLayer.inpainting as _inp
+    if _inp.get_inpaint_func() is None:
+        raise NotImplementedError("layer inpainting (InkLayer/inpainting, diffusers) is outside this build's scope")
+    from InkLayer.inpainting.inpaint_single_layer import inpaint_single_layer
+    image_name, layer_path, prompt = request_data.get("image_name"), request_data.get("layer_path"), request_data.get("prompt")
+    base_dir = os.path.join(cur_dir, f"static/outputs/{image_name}")
+    layer_id = os.path.basename(layer_path).split("_")[-1].split(".")[0]
+    mask = Image.open(os.path.join(base_dir, "masks_disjoint", f"mask_{layer_id}.png")).convert("L")
+    expanded_mask_path = os.path.join(out_dir, f"mask_expanded_{layer_id}.png")
+    bbox = mask.getbbox()
+    if bbox:
+        x0, y0, x1, y1 = bbox
+        x0, y0 = max(0, x0 - 10), max(0, y0 - 10)
+        x1, y1 = min(mask.width, x1 + 10), min(mask.height, y1 + 10)
+        expanded = Image.new("L", mask.size, 0)
+        ImageDraw.Draw(expanded).rectangle([x0, y0, x1, y1], fill=255)
+        expanded.save(expanded_mask_path)
+    else:
+        mask.save(expanded_mask_path)
+    return inpaint_single_layer(image_path=os.path.join(base_dir, "input.png"), mask_path=expanded_mask_path,
+                                output_dir=out_dir, prompt=prompt, layer_id=layer_id)

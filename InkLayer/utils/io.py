@@ -2,7 +2,7 @@
 cv2): a minimal PNG writer whose compression step is `zlib.compress` - it releases the GIL, so the dozens of mask files
 of a sketch are encoded on a small thread pool - for the three pixel formats the runner's tree uses: bool [H, W] ->
 1-bit grayscale (what PIL writes for mode "1" and reads back as mode "1"), uint8 [H, W] -> 8-bit grayscale (mode "L"),
-uint8 [H, W, 3] -> RGB.  Pixels are stored losslessly, like any PNG; only the compression level (1, cv2.imwrite's
+uint8 [H, W, 3] -> RGB (and uint8 [H, W, 4] -> RGBA, for the layer stage).  Pixels are stored losslessly, like any PNG; only the compression level (1, cv2.imwrite's
 default ballpark) differs from PIL's default."""
 import struct
 import zlib
@@ -23,6 +23,8 @@ def png_bytes(a: np.ndarray, level: int = 1) -> bytes:
         rows, depth, ctype = a, 8, 0
     elif a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
         rows, depth, ctype = a.reshape(h, w * 3), 8, 2
+    elif a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 4:
+        rows, depth, ctype = a.reshape(h, w * 4), 8, 6
     else:
         raise ValueError(f"png_bytes: unsupported array {a.dtype} {a.shape}")
     raw = np.empty((h, rows.shape[1] + 1), np.uint8)

@@ -619,6 +619,79 @@ int ink_resize_bilinear_ac_nhwc(const float* in, int32_t B, int32_t h, int32_t w
 int ink_im2col3x3_ex_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t relu,
                          void* out_f16, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Layer assembly: the reference's inpainting stage around the diffusion model.  Binary images are
+ * row-aligned bit planes [n, H, ceil(W / 64)] uint64 (bit b of word w = pixel 64 w + b), n <= 254, H, W <= 16383.
+ * All results are integers and bit-exact against tests/layers_ref.py.  These entry points were added without changing
+ * any existing one.
+ *
+ * ink_layers_otsu_planes: grey images uint8 [n, H, W] -> hist int32 [n, 256] of v (or 255 - v when invert != 0:
+ * cv2.bitwise_not, fill_object_bg_mask.py:63-65), Otsu's threshold per image from the 256 counts in float64 as cv2
+ * evaluates it (first maximum, strict >; fill_object_bg_mask.py:68-69) -> thresh int32 [n], planes = v > thresh. */
+int ink_layers_otsu_planes(const void* gray_u8, int32_t n, int32_t H, int32_t W, int32_t invert, int32_t* hist,
+                           int32_t* thresh, void* out_planes, void* stream);
+
+/* cv2.dilate(planes, getStructuringElement(MORPH_ELLIPSE, (k, k)), iterations) for k = 3 (a cross) or 5 (rows of half
+ * width 0, 2, 2, 2, 0); pixels outside the image never count (fill_object_bg_mask.py:71-73, 84).  tmp_planes: n planes. */
+int ink_layers_dilate(const void* planes, int32_t n, int32_t H, int32_t W, int32_t kernel_size, int32_t iterations,
+                      void* tmp_planes, void* out_planes, void* stream);
+
+/* flags[p] = 1 iff plane p has a pixel in the first / last `band` rows or columns (fill_object_bg_mask.py:76-81). */
+int ink_layers_border_band(const void* planes, int32_t n, int32_t H, int32_t W, int32_t band, int32_t* flags,
+                           void* stream);
+
+/* Component passes of get_mask.  mode 0: out = the silhouette ~flooded | planes, flooded = planes with the 4-connected
+ * background component holding pixel (0, 0) set (cv2.floodFill from (0, 0), fill_object_bg_mask.py:91-93).  mode 1: out = planes with every hole filled
+ * (fill_enclosed_regions, :4-20; a hole = a 4-connected background component that does not reach the image edge).
+ * mode 2: fill_holes_not_touching_border (:22-47): a hole is filled, with everything it surrounds, when its box grown by
+ * one stays off the image edge and its contour area is >= 50.  mode 3: the 8-connected component of largest contour
+ * area with what it surrounds (:96-100; equal areas: the one whose first pixel comes last in raster order); its input
+ * must hold no enclosed background, as a flooded silhouette does.  Contour area = polygon through the pixel centres of
+ * the followed border, evaluated in closed form per 2x2 cell.  In mode 2 a small hole that surrounds foreground islands
+ * may stay undecided: workspace[1] = number of such holes, workspace[2 + 8 k ..] = (plane, xmin, xmax, ymin, ymax,
+ * twice the area of the hole's own cells, y and x of the hole's first pixel) for the first 64; they are left unfilled for the caller to resolve.
+ * workspace[0] != 0: run table overflow (cannot happen with the queried size).  tmp_planes3: 3 n planes. */
+int ink_layers_components_workspace_ints(int32_t n, int32_t H, int32_t W, int64_t* out_ints);
+int ink_layers_components(const void* planes, int32_t n, int32_t H, int32_t W, int32_t mode, void* tmp_planes3,
+                          int32_t* workspace, void* out_planes, void* stream);
+
+/* cv2.distanceTransform(mask, DIST_L2, 5) as int32 16.16 fixed point [n, H, W] (weights 65536, 91750, 143976; zero
+ * pixels inside the image only; 0x1fffffff where no zero pixel is reachable), then fill_object_bg_mask.py:103-107:
+ * min_out[p] = smallest distance over the pixels of stroke plane p, shrink_out[p] = max(0, floor(float32(min) / 65536)
+ * - safety_margin), out plane = shrink > 0 ? float32(dist) / 65536 >= shrink : mask.  Tiled relaxation repeated until
+ * nothing below min + 1 pixel changes any more (full != 0: until nothing changes, so that `dist` is exact everywhere;
+ * otherwise it is exact below that bound and an upper bound above it). */
+int ink_layers_chamfer_workspace_ints(int32_t n, int32_t H, int32_t W, int64_t* out_ints);
+int ink_layers_chamfer(const void* mask_planes, const void* stroke_planes, int32_t n, int32_t H, int32_t W,
+                       int32_t safety_margin, int32_t full, int32_t* dist, int32_t* workspace, int32_t* min_out,
+                       int32_t* shrink_out, void* out_planes, void* stream);
+
+/* bbox int32 [n, 4] = mask_to_bbox (util.py:198-204: pixels > 127, INCLUSIVE maxima; (W, H, -1, -1) when empty);
+ * overlap int32 [n, n]: [i, j] = 1 iff j < i and mask i (> 0) has a pixel inside box j sliced EXCLUSIVELY
+ * (util.py:39-55, 148-157). */
+int ink_layers_mask_tables(const void* masks_u8, int32_t n, int32_t H, int32_t W, int32_t* bbox, int32_t* overlap,
+                           void* stream);
+
+/* Per layer i (util.py:31-34, 94-104, 242-260): sketch_layers uint8 [n, H, W, 3] = the sketch's (B, G, R) inside mask i
+ * and 255 outside; edit_masks uint8 [n, H, W] = 0 / 255: OR of bg_planes[j] over overlap[i, j], inside box i sliced
+ * exclusively, minus mask i; debug uint8 [n, H, W, 3]: 255 on the mask, (0, 0, 255) on the edit mask. */
+int ink_layers_assemble(const void* sketch_rgb_u8, const void* masks_u8, const void* bg_planes, const int32_t* bbox,
+                        const int32_t* overlap, int32_t n, int32_t H, int32_t W, void* sketch_layers_u8,
+                        void* edit_masks_u8, void* debug_u8, void* stream);
+
+/* composite_original_sketch_onto_inpainted (util.py:101, 109-133): out = inpainted (R, G, B), replaced by the sketch
+ * layer's pixel swapped back to (R, G, B) wherever one of its channels is < 255. */
+int ink_layers_composite(const void* inpainted_rgb_u8, const void* sketch_layer_u8, int32_t H, int32_t W,
+                         void* out_rgb_u8, void* stream);
+
+/* cv2.imread(IMREAD_GRAYSCALE) of 8-bit RGB pixels [n, H, W, 3] -> [n, H, W] (fill_object_bg_mask.py:63, 136). */
+int ink_layers_gray(const void* rgb_u8, int32_t n, int32_t H, int32_t W, void* gray_u8, void* stream);
+
+/* create_rgba_with_background_mask (fill_object_bg_mask.py:141, 165-177): rgba uint8 [n, H, W, 4]: alpha = 255 where
+ * grey < 240 or the background plane is set; colour = grey on those sketch pixels, else 255 on the background, else 0. */
+int ink_layers_rgba(const void* gray_u8, const void* bg_planes, int32_t n, int32_t H, int32_t W, void* rgba_u8,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

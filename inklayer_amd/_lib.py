@@ -134,6 +134,20 @@ SIGNATURES = {
                            c_int, c_void_p, c_void_p],
     "ink_resize_bilinear_ac_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_im2col3x3_ex_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_layers_otsu_planes": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_layers_dilate": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_layers_border_band": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_layers_components_workspace_ints": [c_int, c_int, c_int, C.POINTER(c_i64)],
+    "ink_layers_components": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_layers_chamfer_workspace_ints": [c_int, c_int, c_int, C.POINTER(c_i64)],
+    "ink_layers_chamfer": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p],
+    "ink_layers_mask_tables": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_layers_assemble": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p, c_void_p],
+    "ink_layers_composite": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "ink_layers_gray": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_layers_rgba": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_relpos_bias": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }

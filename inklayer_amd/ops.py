@@ -1102,3 +1102,147 @@ def im2col3x3_ex(x: torch.Tensor, B: int, H: int, W: int, stride: int = 1, relu:
     check(_lib.lib().ink_im2col3x3_ex_f16(x.data_ptr(), B, H, W, Cn, stride, int(relu), out.data_ptr(), _stream()),
           "ink_im2col3x3_ex_f16")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Layer assembly (DESIGN §0 row (f)-5): bit planes are int64 [n, H, ceil(W / 64)], images uint8
+# ---------------------------------------------------------------------------------------------
+def _planes_like(n: int, H: int, W: int, dev) -> torch.Tensor:
+    return torch.empty((n, H, (W + 63) // 64), device=dev, dtype=torch.int64)
+
+
+def _check_planes(p: torch.Tensor, W: int):
+    assert p.dtype == torch.int64 and p.is_cuda and p.is_contiguous() and p.dim() == 3 and p.shape[2] == (W + 63) // 64
+    return int(p.shape[0]), int(p.shape[1])
+
+
+def layers_otsu_planes(gray_u8: torch.Tensor, invert: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """[n, H, W] uint8 -> (planes of v > Otsu(v), hist int32 [n, 256], thresh int32 [n]); v = 255 - grey if invert."""
+    assert gray_u8.dtype == torch.uint8 and gray_u8.is_cuda and gray_u8.is_contiguous() and gray_u8.dim() == 3
+    n, H, W = (int(v) for v in gray_u8.shape)
+    dev = gray_u8.device
+    hist = torch.empty((n, 256), device=dev, dtype=torch.int32)
+    thresh = torch.empty(n, device=dev, dtype=torch.int32)
+    planes = _planes_like(n, H, W, dev)
+    check(_lib.lib().ink_layers_otsu_planes(gray_u8.data_ptr(), n, H, W, int(invert), hist.data_ptr(), thresh.data_ptr(),
+                                            planes.data_ptr(), _stream()), "ink_layers_otsu_planes")
+    return planes, hist, thresh
+
+
+def layers_dilate(planes: torch.Tensor, W: int, kernel_size: int, iterations: int) -> torch.Tensor:
+    """cv2.dilate with the k x k ellipse (k = 3 or 5), `iterations` times."""
+    n, H = _check_planes(planes, W)
+    if iterations <= 0:
+        return planes.clone()
+    tmp, out = torch.empty_like(planes), torch.empty_like(planes)
+    check(_lib.lib().ink_layers_dilate(planes.data_ptr(), n, H, W, kernel_size, iterations, tmp.data_ptr(), out.data_ptr(),
+                                       _stream()), "ink_layers_dilate")
+    return out
+
+
+def layers_border_band(planes: torch.Tensor, W: int, band: int) -> torch.Tensor:
+    """int32 [n]: 1 where the plane has a pixel within `band` of an image edge."""
+    n, H = _check_planes(planes, W)
+    flags = torch.empty(n, device=planes.device, dtype=torch.int32)
+    check(_lib.lib().ink_layers_border_band(planes.data_ptr(), n, H, W, band, flags.data_ptr(), _stream()),
+          "ink_layers_border_band")
+    return flags
+
+
+LAYERS_MODES = {"flood": 0, "fill_all": 1, "fill_rule": 2, "largest": 3}
+
+
+def layers_components(planes: torch.Tensor, W: int, mode: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One component pass of get_mask (see ink_layers_components) -> (planes, workspace header int32 [514]:
+    [0] overflow flag, [1] number of undecided holes of mode 'fill_rule', then their 8-int records)."""
+    n, H = _check_planes(planes, W)
+    need = C.c_int64(0)
+    check(_lib.lib().ink_layers_components_workspace_ints(n, H, W, C.byref(need)), "ink_layers_components_workspace_ints")
+    ws = torch.empty(need.value, device=planes.device, dtype=torch.int32)
+    tmp = torch.empty((3,) + tuple(planes.shape), device=planes.device, dtype=torch.int64)
+    out = torch.empty_like(planes)
+    check(_lib.lib().ink_layers_components(planes.data_ptr(), n, H, W, LAYERS_MODES[mode], tmp.data_ptr(), ws.data_ptr(),
+                                           out.data_ptr(), _stream()), "ink_layers_components")
+    return out, ws[:514]
+
+
+def layers_chamfer(mask_planes: torch.Tensor, stroke_planes: torch.Tensor, W: int, safety_margin: int = 0,
+                   full: bool = False):
+    """5x5 chamfer distance int32 16.16 [n, H, W] of the planes + get_mask's shrink step ->
+    (dist, min over the stroke pixels int32 [n], shrink_by int32 [n], thresholded planes)."""
+    n, H = _check_planes(mask_planes, W)
+    assert _check_planes(stroke_planes, W) == (n, H)
+    dev = mask_planes.device
+    need = C.c_int64(0)
+    check(_lib.lib().ink_layers_chamfer_workspace_ints(n, H, W, C.byref(need)), "ink_layers_chamfer_workspace_ints")
+    ws = torch.empty(need.value, device=dev, dtype=torch.int32)
+    dist = torch.empty((n, H, W), device=dev, dtype=torch.int32)
+    mn = torch.empty(n, device=dev, dtype=torch.int32)
+    shrink = torch.empty(n, device=dev, dtype=torch.int32)
+    out = torch.empty_like(mask_planes)
+    check(_lib.lib().ink_layers_chamfer(mask_planes.data_ptr(), stroke_planes.data_ptr(), n, H, W, safety_margin, int(full),
+                                        dist.data_ptr(), ws.data_ptr(), mn.data_ptr(), shrink.data_ptr(), out.data_ptr(),
+                                        _stream()), "ink_layers_chamfer")
+    return dist, mn, shrink, out
+
+
+def layers_mask_tables(masks_u8: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[n, H, W] uint8 -> (bbox int32 [n, 4] with inclusive maxima, overlap int32 [n, n])."""
+    assert masks_u8.dtype == torch.uint8 and masks_u8.is_cuda and masks_u8.is_contiguous() and masks_u8.dim() == 3
+    n, H, W = (int(v) for v in masks_u8.shape)
+    bbox = torch.empty((n, 4), device=masks_u8.device, dtype=torch.int32)
+    overlap = torch.empty((n, n), device=masks_u8.device, dtype=torch.int32)
+    check(_lib.lib().ink_layers_mask_tables(masks_u8.data_ptr(), n, H, W, bbox.data_ptr(), overlap.data_ptr(), _stream()),
+          "ink_layers_mask_tables")
+    return bbox, overlap
+
+
+def layers_assemble(sketch_rgb_u8: torch.Tensor, masks_u8: torch.Tensor, bg_planes: torch.Tensor, bbox: torch.Tensor,
+                    overlap: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (sketch layers uint8 [n, H, W, 3] in (B, G, R), edit masks uint8 [n, H, W], debug images uint8 [n, H, W, 3])."""
+    assert masks_u8.dtype == torch.uint8 and masks_u8.is_cuda and masks_u8.is_contiguous() and masks_u8.dim() == 3
+    n, H, W = (int(v) for v in masks_u8.shape)
+    assert sketch_rgb_u8.dtype == torch.uint8 and sketch_rgb_u8.is_cuda and sketch_rgb_u8.is_contiguous()
+    assert tuple(sketch_rgb_u8.shape) == (H, W, 3) and _check_planes(bg_planes, W) == (n, H)
+    assert bbox.dtype == torch.int32 and tuple(bbox.shape) == (n, 4) and bbox.is_contiguous() and bbox.is_cuda
+    assert overlap.dtype == torch.int32 and tuple(overlap.shape) == (n, n) and overlap.is_contiguous() and overlap.is_cuda
+    dev = masks_u8.device
+    sketch = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    edit = torch.empty((n, H, W), device=dev, dtype=torch.uint8)
+    debug = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    check(_lib.lib().ink_layers_assemble(sketch_rgb_u8.data_ptr(), masks_u8.data_ptr(), bg_planes.data_ptr(), bbox.data_ptr(),
+                                         overlap.data_ptr(), n, H, W, sketch.data_ptr(), edit.data_ptr(), debug.data_ptr(),
+                                         _stream()), "ink_layers_assemble")
+    return sketch, edit, debug
+
+
+def layers_composite(inpainted_rgb_u8: torch.Tensor, sketch_layer_u8: torch.Tensor) -> torch.Tensor:
+    """The inpainted image with the sketch layer's own pixels put back (R, G, B)."""
+    for t in (inpainted_rgb_u8, sketch_layer_u8):
+        assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3
+    assert inpainted_rgb_u8.shape == sketch_layer_u8.shape
+    H, W = int(inpainted_rgb_u8.shape[0]), int(inpainted_rgb_u8.shape[1])
+    out = torch.empty_like(inpainted_rgb_u8)
+    check(_lib.lib().ink_layers_composite(inpainted_rgb_u8.data_ptr(), sketch_layer_u8.data_ptr(), H, W, out.data_ptr(),
+                                          _stream()), "ink_layers_composite")
+    return out
+
+
+def layers_gray(rgb_u8: torch.Tensor) -> torch.Tensor:
+    """[n, H, W, 3] uint8 (R, G, B) -> the grey image cv2.imread(IMREAD_GRAYSCALE) gives, [n, H, W]."""
+    assert rgb_u8.dtype == torch.uint8 and rgb_u8.is_cuda and rgb_u8.is_contiguous() and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
+    n, H, W = (int(v) for v in rgb_u8.shape[:3])
+    gray = torch.empty((n, H, W), device=rgb_u8.device, dtype=torch.uint8)
+    check(_lib.lib().ink_layers_gray(rgb_u8.data_ptr(), n, H, W, gray.data_ptr(), _stream()), "ink_layers_gray")
+    return gray
+
+
+def layers_rgba(gray_u8: torch.Tensor, bg_planes: torch.Tensor) -> torch.Tensor:
+    """-> uint8 [n, H, W, 4]: the RGBA layers."""
+    assert gray_u8.dtype == torch.uint8 and gray_u8.is_cuda and gray_u8.is_contiguous() and gray_u8.dim() == 3
+    n, H, W = (int(v) for v in gray_u8.shape)
+    assert _check_planes(bg_planes, W) == (n, H)
+    rgba = torch.empty((n, H, W, 4), device=gray_u8.device, dtype=torch.uint8)
+    check(_lib.lib().ink_layers_rgba(gray_u8.data_ptr(), bg_planes.data_ptr(), n, H, W, rgba.data_ptr(), _stream()),
+          "ink_layers_rgba")
+    return rgba
