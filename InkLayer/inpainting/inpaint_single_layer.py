@@ -1,5 +1,7 @@
-"""Reference surface: InkLayer/inpainting/inpaint_single_layer.py with the registered inpainting function in place of
-the ControlNet pipeline (the text prompt is not passed on: the registered signature has no prompt)."""
+"""Reference surface: InkLayer/inpainting/inpaint_single_layer.py.  With a ControlNet pipe registered
+(InkLayer.inpainting.set_diffusion_pipe) it is the reference's path, text prompt included, around that pipe
+(inklayer_amd/inpaint.py).  With a function registered (set_inpaint_func, which has priority) the function stands in for
+the whole model call and the text prompt is not passed on: the registered signature has no prompt."""
 import os
 
 import numpy as np
@@ -10,11 +12,22 @@ import InkLayer.inpainting as _reg
 
 def inpaint_single_layer(image_path: str, mask_path: str, output_dir: str, prompt: str, layer_id: str,
                          position_data=None):
-    fn = _reg.require_inpaint_func("InkLayer.inpainting.inpaint_single_layer.inpaint_single_layer")
+    me = "InkLayer.inpainting.inpaint_single_layer.inpaint_single_layer"
+    fn = _reg.get_inpaint_func()
+    pipe = _reg.get_diffusion_pipe("controlnet") if fn is None else None
+    if fn is None and pipe is None:
+        fn = _reg.require_inpaint_func(me)       # raises, unless an SDXL pipe is all there is: then it stands in as a function
     image = Image.open(image_path).convert("RGB")
     mask = Image.open(mask_path).convert("L")
     if position_data:
         mask = _move_mask(mask, position_data, image.size)
+    if pipe is not None:                                      # inpaint_single_layer.py:34-85
+        from inklayer_amd import inpaint
+        result, rgba = inpaint.single_layer_inpaint(pipe, image, mask, prompt)
+        result.save(os.path.join(output_dir, f"inpainted_layer_{layer_id}.png"))
+        layer_rgba_path = os.path.join(output_dir, f"layer_{layer_id}_rgba.png")
+        rgba.save(layer_rgba_path)
+        return layer_rgba_path
     result = fn(input_image=image, mask_image=mask).convert("RGB")
     if result.size != image.size:
         result = result.resize(image.size, Image.LANCZOS)

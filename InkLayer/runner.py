@@ -3,8 +3,9 @@ for the detector -> segmentor part:  <out_base_dir>/<name>/{input.png, bboxes.js
 segmented_sketch.png, bboxes.png, masks_cleaned/, bboxes_final.json, bboxes_final.png, masks_disjoint/, masks_final/,
 depth_map.png, segmented_sketch_final.png}.  Detector, segmentor, mask cleanup, sketch-NMS pair table and the depth model
 run on the GPU; so does the layer assembly around the inpainting model (complete_layers/, complete_layers_process/,
-complete_layers_rgba/) once a model function is registered with InkLayer.inpainting.set_inpaint_func - the diffusion model
-itself is not part of this build, and without a function the step is skipped with a message."""
+complete_layers_rgba/) and the pre- and post-processing around the model call, once a diffusers pipe is registered with
+InkLayer.inpainting.set_diffusion_pipe or a model function with set_inpaint_func - the diffusion model itself is not part
+of this build, and with neither the step is skipped with a message."""
 import os
 import shutil
 
@@ -123,8 +124,9 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
         run_refinement_on_sketch_dir(out_dir, bbox_out_path, cleaned_masks=cleaned, sketch_rgb=rgb)
         _tick("depth + refinement stage + masks_disjoint/ masks_final/ (files)", t0)
         import InkLayer.inpainting as _inp
-        if inpaint and _inp.get_inpaint_func() is not None:
-            # Layer assembly (runner.py:79-84) around the registered inpainting function, from the final masks the
+        inpaint_func = _inp.resolve_inpaint_func() if inpaint else None
+        if inpaint_func is not None:
+            # Layer assembly (runner.py:79-84) around the registered inpainting function or pipe, from the final masks the
             # refinement stage just produced (not re-read from masks_final/, whose files may still be in the I/O queue)
             t0 = time.perf_counter()
             from InkLayer.inpainting.util import write_layers
@@ -133,7 +135,7 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
             assert held_dir == os.path.abspath(out_dir), "the refinement stage did not leave this sketch's final masks"
             masks_u8 = np.stack([(np.asarray(m) > 0).astype(np.uint8) * 255 for m in final_masks]) if len(final_masks) \
                 else np.zeros((0,) + rgb.shape[:2], np.uint8)
-            inpainted_dir, layer_pixels = write_layers(out_dir, rgb, masks_u8, _inp.get_inpaint_func())
+            inpainted_dir, layer_pixels = write_layers(out_dir, rgb, masks_u8, inpaint_func)
             print(f"Inpainting completed. Output saved to {inpainted_dir}")
             rgba_layers_to_dir(layer_pixels, inpainted_dir.replace("layers", "layers_rgba"))
             _tick("layer assembly + inpainting function + RGBA layers (GPU + files)", t0)
@@ -169,9 +171,10 @@ def run_inklayer_pipeline(input_path, out_base_dir, no_intermediate=False, inpai
 
 
 def run_inpaint_single_layer(request_data, cur_dir, out_dir):
-    """runner.py:104-172: the layer's mask grown to its box + 10 px, handed to the registered inpainting function."""
+    """runner.py:104-172: the layer's mask grown to its box + 10 px, handed to the registered pipe (with the prompt) or
+    to the registered inpainting function."""
     import InkLayer.inpainting as _inp
-    if _inp.get_inpaint_func() is None:
+    if _inp.resolve_inpaint_func() is None:
         raise NotImplementedError("layer inpainting (InkLayer/inpainting, diffusers) is outside this build's scope")
     from InkLayer.inpainting.inpaint_single_layer import inpaint_single_layer
     image_name, layer_path, prompt = request_data.get("image_name"), request_data.get("layer_path"), request_data.get("prompt")

@@ -692,6 +692,67 @@ int ink_layers_gray(const void* rgb_u8, int32_t n, int32_t H, int32_t W, void* g
 int ink_layers_rgba(const void* gray_u8, const void* bg_planes, int32_t n, int32_t H, int32_t W, void* rgba_u8,
                     void* stream);
 
+/* ------------------------------------------------------------------------
+ * Inpainting: pre- and post-processing around the diffusion pipe (csrc/inpaint_ops.hip).  Images are
+ * uint8 [H, W, 3] (R, G, B) and uint8 [H, W] on the device.  Every table of exponentials is computed on the host in
+ * double precision, rounded once to the stated type and passed in; the kernels do + - x /, compares and conversions in
+ * a fixed order and equal tests/inpaint_ref.py bit for bit.  The stencil entry points need H, W >= 3.
+ * ------------------------------------------------------------------------ */
+
+/* ImageEnhance.Contrast(image).enhance(factor) (inpaint_ControlNet.py:51-54): mean = round-half-up mean of Pillow's L
+ * image from an integer sum kept on the device (sum_u64: 8 bytes of workspace), then
+ * clip(float(mean) + factor * float(v - mean)) in f32, truncated. */
+int ink_inp_contrast(const void* rgb_u8, int32_t H, int32_t W, float factor, void* sum_u64, void* out_rgb_u8,
+                     void* stream);
+
+/* cv2.bilateralFilter(rgb, 5, 50, 50) (inpaint_ControlNet.py:56-63): 13 taps of the radius-2 disc in row-major order,
+ * reflect-101; tables: f32 [13 + 768] = the space weights of the taps, then the colour weights by |db| + |dg| + |dr|.
+ * w = space * colour, sums in f32 in tap order, out = rint(sum * (1 / wsum)).  Not in place. */
+int ink_inp_bilateral(const void* rgb_u8, int32_t H, int32_t W, const float* tables, void* out_rgb_u8, void* stream);
+
+/* preprocess_mask (inpaint_ControlNet.py:67-75): dilate_iterations x cv2.dilate with a 3x3 block of ones, then (blur = 1)
+ * cv2.GaussianBlur((3, 3), 0) = ([1 2 1]^T [1 2 1] . p + 8) >> 4 with a reflect-101 border.  tmp2_u8: 2 H W bytes.
+ * At least one of the two steps must be asked for; not in place. */
+int ink_inp_mask_prepare(const void* mask_u8, int32_t H, int32_t W, int32_t dilate_iterations, int32_t blur,
+                         void* tmp2_u8, void* out_u8, void* stream);
+
+/* Pillow's 8-bit two-pass resampler for 1 or 3 interleaved channels and any of its filters: Image.resize(LANCZOS) of
+ * inpaint_ControlNet.py:150-151, 161, 176 and inpaint_single_layer.py:43-44, 63, the default bicubic resize of
+ * inpaint_SDXL.py:23-24.  Tables as for ink_resize_bilinear_u8, built by inklayer_amd/resize.py::pil_resize_coeffs for
+ * the filter; tmp_u8 [h, ow, channels] when both sizes change.  The same size on both axes is a copy. */
+int ink_inp_resize_u8(const void* src_u8, int32_t h, int32_t w, int32_t channels, void* dst_u8, int32_t oh, int32_t ow,
+                      const int32_t* xbounds, const int32_t* xcoef, int32_t kx, const int32_t* ybounds,
+                      const int32_t* ycoef, int32_t ky, void* tmp_u8, void* stream);
+
+/* make_inpaint_condition (inpaint_ControlNet.py:77-90): f32 [3, H, W] planar = v / 255, -1 where mask >= 128. */
+int ink_inp_condition(const void* rgb_u8, const void* mask_u8, int32_t H, int32_t W, float* out_f32, void* stream);
+
+/* _adaptive_threshold_blend, first half (inpaint_ControlNet.py:99-116): cv2 grey, its 11x11 Gaussian (sigma 2) in f32
+ * with a replicated border (taps11: f32 [11]; rows left to right, columns from the centre outwards; tmp_f32 [H, W]),
+ * rounded half-even to u8 = mean; thresh = 255 where grey > mean - 2, else 0; clean = 255 where thresh, else the pixel. */
+int ink_inp_cleanup(const void* result_rgb_u8, int32_t H, int32_t W, const float* taps11, float* tmp_f32,
+                    void* thresh_u8, void* clean_rgb_u8, void* stream);
+
+/* _adaptive_threshold_blend, second half (inpaint_ControlNet.py:118-124) in f64: soft = clip(3x3 Gaussian (sigma 1) of
+ * mask / 255, 0, 1), reflect-101, taps2: f64 [2] = centre and side weight, tmp_f64 [H, W];
+ * out = trunc(clean * soft + original * (1 - soft)). */
+int ink_inp_soft_blend(const void* clean_rgb_u8, const void* original_rgb_u8, const void* mask_u8, int32_t H, int32_t W,
+                       const double* taps2, double* tmp_f64, void* out_rgb_u8, void* stream);
+
+/* image.convert("L") (out_channels 1) and .convert("L").convert("RGB") (3) (inpaint_ControlNet.py:181,
+ * inpaint_SDXL.py:32): (19595 R + 38470 G + 7471 B + 0x8000) >> 16. */
+int ink_inp_luma(const void* rgb_u8, int32_t H, int32_t W, int32_t out_channels, void* out_u8, void* stream);
+
+/* ImageFilter.UnsharpMask with a blur radius whose box radius is below 1 (inpaint_ControlNet.py:182: radius 0.5):
+ * three box passes along x and three along y, (ww p + fw (p[-1] + p[+1]) + 2^23) >> 24 each stored as u8, replicated
+ * border; then d = in - blur, out = clip(in + d * percent / 100) where |d| > threshold (C division), else in.
+ * fw must be (2^24 - ww) / 2; tmp2_u8: 2 H W channels bytes. */
+int ink_inp_unsharp(const void* img_u8, int32_t H, int32_t W, int32_t channels, uint32_t ww, uint32_t fw,
+                    int32_t percent, int32_t threshold, void* tmp2_u8, void* out_u8, void* stream);
+
+/* The RGBA layer of inpaint_single_layer.py:74-78: the result with alpha 255 where mask > 128, zeros elsewhere. */
+int ink_inp_rgba_cut(const void* rgb_u8, const void* mask_u8, int32_t H, int32_t W, void* rgba_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

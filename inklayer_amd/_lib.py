@@ -148,6 +148,17 @@ SIGNATURES = {
     "ink_layers_composite": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_layers_gray": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_layers_rgba": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_inp_contrast": [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
+    "ink_inp_bilateral": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_inp_mask_prepare": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_inp_resize_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                          c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "ink_inp_condition": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "ink_inp_cleanup": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_inp_soft_blend": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_inp_luma": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_inp_unsharp": [c_void_p, c_int, c_int, c_int, C.c_uint32, C.c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_inp_rgba_cut": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_relpos_bias": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }

@@ -1246,3 +1246,139 @@ def layers_rgba(gray_u8: torch.Tensor, bg_planes: torch.Tensor) -> torch.Tensor:
     check(_lib.lib().ink_layers_rgba(gray_u8.data_ptr(), bg_planes.data_ptr(), n, H, W, rgba.data_ptr(), _stream()),
           "ink_layers_rgba")
     return rgba
+
+
+# ---------------------------------------------------------------------------------------------
+# Inpainting pre- and post-processing (csrc/inpaint_ops.hip): uint8 [H, W, 3] (R, G, B) and uint8 [H, W]
+# ---------------------------------------------------------------------------------------------
+def _check_img(t: torch.Tensor, channels: int, what: str) -> Tuple[int, int]:
+    assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), f"{what}: contiguous uint8 CUDA tensor expected"
+    if channels == 1:
+        assert t.dim() == 2, f"{what}: [H, W] expected"
+    else:
+        assert t.dim() == 3 and t.shape[2] == channels, f"{what}: [H, W, {channels}] expected"
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _stencil_size(H: int, W: int, what: str) -> None:
+    if H < 3 or W < 3:
+        raise ValueError(f"{what}: images smaller than 3 pixels on a side are not supported (got {W}x{H})")
+
+
+def inp_contrast(rgb_u8: torch.Tensor, factor: float = 1.2) -> torch.Tensor:
+    """ImageEnhance.Contrast(image).enhance(factor), bit for bit."""
+    H, W = _check_img(rgb_u8, 3, "inp_contrast")
+    _stencil_size(H, W, "inp_contrast")
+    ws = torch.empty(1, device=rgb_u8.device, dtype=torch.int64)
+    out = torch.empty_like(rgb_u8)
+    check(_lib.lib().ink_inp_contrast(rgb_u8.data_ptr(), H, W, float(factor), ws.data_ptr(), out.data_ptr(), _stream()),
+          "ink_inp_contrast")
+    return out
+
+
+def inp_bilateral(rgb_u8: torch.Tensor, tables: torch.Tensor) -> torch.Tensor:
+    """cv2.bilateralFilter(rgb, 5, sigma, sigma); tables f32 [13 + 768] from inpaint.bilateral_tables."""
+    H, W = _check_img(rgb_u8, 3, "inp_bilateral")
+    _stencil_size(H, W, "inp_bilateral")
+    assert tables.dtype == F32 and tables.is_cuda and tables.is_contiguous() and tables.numel() == 13 + 768
+    out = torch.empty_like(rgb_u8)
+    check(_lib.lib().ink_inp_bilateral(rgb_u8.data_ptr(), H, W, tables.data_ptr(), out.data_ptr(), _stream()),
+          "ink_inp_bilateral")
+    return out
+
+
+def inp_mask_prepare(mask_u8: torch.Tensor, dilate_iterations: int = 1, blur: bool = True) -> torch.Tensor:
+    """preprocess_mask: 3x3 dilation `dilate_iterations` times, then cv2.GaussianBlur((3, 3), 0)."""
+    H, W = _check_img(mask_u8, 1, "inp_mask_prepare")
+    _stencil_size(H, W, "inp_mask_prepare")
+    if dilate_iterations <= 0 and not blur:
+        return mask_u8.clone()
+    tmp = torch.empty((2, H, W), device=mask_u8.device, dtype=torch.uint8)
+    out = torch.empty_like(mask_u8)
+    check(_lib.lib().ink_inp_mask_prepare(mask_u8.data_ptr(), H, W, max(int(dilate_iterations), 0), int(bool(blur)),
+                                          tmp.data_ptr(), out.data_ptr(), _stream()), "ink_inp_mask_prepare")
+    return out
+
+
+def inp_resize_u8(image_u8: torch.Tensor, oh: int, ow: int, filter: str = "lanczos") -> torch.Tensor:
+    """PIL `Image.resize((ow, oh), filter)` of a uint8 [H, W] or [H, W, 3] CUDA tensor, bit for bit; filter is
+    "bilinear", "bicubic" or "lanczos".  The same size gives a copy."""
+    from .resize import plan_for
+    assert image_u8.dim() in (2, 3)
+    ch = 1 if image_u8.dim() == 2 else 3
+    h, w = _check_img(image_u8, ch, "inp_resize_u8")
+    assert oh > 0 and ow > 0
+    pl = plan_for(h, w, oh, ow, image_u8.device, filter, ch)
+    out = torch.empty((oh, ow) if ch == 1 else (oh, ow, 3), device=image_u8.device, dtype=torch.uint8)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    check(_lib.lib().ink_inp_resize_u8(image_u8.data_ptr(), h, w, ch, out.data_ptr(), oh, ow, ptr(pl.xb), ptr(pl.xk), pl.kx,
+                                       ptr(pl.yb), ptr(pl.yk), pl.ky, ptr(pl.tmp), _stream()), "ink_inp_resize_u8")
+    return out
+
+
+def inp_condition(rgb_u8: torch.Tensor, mask_u8: torch.Tensor) -> torch.Tensor:
+    """make_inpaint_condition -> f32 [1, 3, H, W]."""
+    H, W = _check_img(rgb_u8, 3, "inp_condition")
+    assert _check_img(mask_u8, 1, "inp_condition") == (H, W), "image and mask must have the same dimensions"
+    out = torch.empty((1, 3, H, W), device=rgb_u8.device, dtype=F32)
+    check(_lib.lib().ink_inp_condition(rgb_u8.data_ptr(), mask_u8.data_ptr(), H, W, out.data_ptr(), _stream()),
+          "ink_inp_condition")
+    return out
+
+
+def inp_cleanup(result_rgb_u8: torch.Tensor, taps11: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The adaptive-threshold half of _adaptive_threshold_blend -> (clean uint8 [H, W, 3], thresh uint8 [H, W])."""
+    H, W = _check_img(result_rgb_u8, 3, "inp_cleanup")
+    _stencil_size(H, W, "inp_cleanup")
+    assert taps11.dtype == F32 and taps11.is_cuda and taps11.is_contiguous() and taps11.numel() == 11
+    dev = result_rgb_u8.device
+    tmp = torch.empty((H, W), device=dev, dtype=F32)
+    thresh = torch.empty((H, W), device=dev, dtype=torch.uint8)
+    clean = torch.empty_like(result_rgb_u8)
+    check(_lib.lib().ink_inp_cleanup(result_rgb_u8.data_ptr(), H, W, taps11.data_ptr(), tmp.data_ptr(), thresh.data_ptr(),
+                                     clean.data_ptr(), _stream()), "ink_inp_cleanup")
+    return clean, thresh
+
+
+def inp_soft_blend(clean_rgb_u8: torch.Tensor, original_rgb_u8: torch.Tensor, mask_u8: torch.Tensor,
+                   taps2: torch.Tensor) -> torch.Tensor:
+    """The soft-mask half of _adaptive_threshold_blend (f64)."""
+    H, W = _check_img(clean_rgb_u8, 3, "inp_soft_blend")
+    _stencil_size(H, W, "inp_soft_blend")
+    assert _check_img(original_rgb_u8, 3, "inp_soft_blend") == (H, W) and _check_img(mask_u8, 1, "inp_soft_blend") == (H, W)
+    assert taps2.dtype == torch.float64 and taps2.is_cuda and taps2.is_contiguous() and taps2.numel() == 2
+    tmp = torch.empty((H, W), device=clean_rgb_u8.device, dtype=torch.float64)
+    out = torch.empty_like(clean_rgb_u8)
+    check(_lib.lib().ink_inp_soft_blend(clean_rgb_u8.data_ptr(), original_rgb_u8.data_ptr(), mask_u8.data_ptr(), H, W,
+                                        taps2.data_ptr(), tmp.data_ptr(), out.data_ptr(), _stream()), "ink_inp_soft_blend")
+    return out
+
+
+def inp_luma(rgb_u8: torch.Tensor, out_channels: int = 3) -> torch.Tensor:
+    """image.convert("L") (out_channels 1) or .convert("L").convert("RGB") (3)."""
+    H, W = _check_img(rgb_u8, 3, "inp_luma")
+    assert out_channels in (1, 3)
+    out = torch.empty((H, W) if out_channels == 1 else (H, W, 3), device=rgb_u8.device, dtype=torch.uint8)
+    check(_lib.lib().ink_inp_luma(rgb_u8.data_ptr(), H, W, out_channels, out.data_ptr(), _stream()), "ink_inp_luma")
+    return out
+
+
+def inp_unsharp(image_u8: torch.Tensor, ww: int, fw: int, percent: int = 150, threshold: int = 3) -> torch.Tensor:
+    """ImageFilter.UnsharpMask for a box radius below 1; (ww, fw) from inpaint.box_weights(radius)."""
+    ch = 1 if image_u8.dim() == 2 else 3
+    H, W = _check_img(image_u8, ch, "inp_unsharp")
+    tmp = torch.empty(2 * H * W * ch, device=image_u8.device, dtype=torch.uint8)
+    out = torch.empty_like(image_u8)
+    check(_lib.lib().ink_inp_unsharp(image_u8.data_ptr(), H, W, ch, int(ww), int(fw), int(percent), int(threshold),
+                                     tmp.data_ptr(), out.data_ptr(), _stream()), "ink_inp_unsharp")
+    return out
+
+
+def inp_rgba_cut(rgb_u8: torch.Tensor, mask_u8: torch.Tensor) -> torch.Tensor:
+    """uint8 [H, W, 4]: the image with alpha 255 where mask > 128, zeros elsewhere."""
+    H, W = _check_img(rgb_u8, 3, "inp_rgba_cut")
+    assert _check_img(mask_u8, 1, "inp_rgba_cut") == (H, W)
+    out = torch.empty((H, W, 4), device=rgb_u8.device, dtype=torch.uint8)
+    check(_lib.lib().ink_inp_rgba_cut(rgb_u8.data_ptr(), mask_u8.data_ptr(), H, W, out.data_ptr(), _stream()),
+          "ink_inp_rgba_cut")
+    return out
