@@ -11,7 +11,7 @@ import os
 from typing import Dict, Optional
 
 import numpy as np
-from PIL import Image, ImageDraw
+from PIL import Image
 
 
 def _cleaned_stack(masks_dir: str, count: int, shape) -> np.ndarray:
@@ -51,13 +51,11 @@ def run_postprocess_boxes_on_sketch_dir(sketch_dir, sketch_iou_thresh=0.5, clean
     target = os.path.join(sketch_dir, "bboxes_final.json")
     with open(target, "w") as fh:
         json.dump(kept, fh, indent=4)
-    # bboxes_final.png: a plain visualisation (InkLayer/utils/visualization.py is outside the hot path)
+    # bboxes_final.png (bbox_filter.py:62-69): the kept boxes with their scores, drawn on the I/O threads
     def _visual():
+        from InkLayer.utils.visualization import draw_boxes
         canvas = Image.open(sketch_png).convert("RGB") if sketch_rgb is None else Image.fromarray(sketch_rgb)
-        pen, (W, H) = ImageDraw.Draw(canvas), canvas.size
-        for x1, y1, x2, y2 in kept["bboxes"]:
-            pen.rectangle([x1 * W, y1 * H, x2 * W, y2 * H], outline=(220, 40, 40), width=2)
-        return canvas
+        return draw_boxes(canvas, kept["bboxes"], kept["scores"])
     from InkLayer.utils.io import save_all
     save_all([(_visual, os.path.join(sketch_dir, "bboxes_final.png"))], wait=None)
     print(f"sketch NMS kept {len(kept['bboxes'])} of {len(detections['bboxes'])} boxes -> {target}")

@@ -51,8 +51,19 @@ def match_masks_to_boxes(masks, boxes):
 
 
 def _colour(rgb, masks):
-    from InkLayer.runner import colour_by_masks
-    return Image.fromarray(colour_by_masks(rgb, masks))
+    """color_sketch_by_masks of the reference (refiner.py:342-362) as a PIL image; the kernels run on the caller's thread."""
+    from inklayer_amd.visualize import colour_sketch
+    return Image.fromarray(colour_sketch(rgb, masks))
+
+
+def _colour_labels(rgb, label, n, extra=None):
+    """The same picture from a label image (l = mask l - 1) with the appended "unlabeled" mask as label n + 1
+    -> uint8 [H, W, 3] on the host."""
+    from inklayer_amd.visualize import colour_sketch
+    if extra is not None:
+        label = np.where(np.asarray(extra) != 0, np.uint8(n + 1), label).astype(np.uint8)
+        n += 1
+    return colour_sketch(rgb, np.ascontiguousarray(label), n_labels=n)
 
 
 def improve_sam_masks(sketch_image_path, masks_np, bboxes):
@@ -74,7 +85,8 @@ def improve_sam_masks(sketch_image_path, masks_np, bboxes):
     final_masks = [final == l for l in range(1, len(masks_np) + 1)]
     if extra is not None:
         final_masks.append(extra.astype(np.uint8))
-    return {"initial_seg_sketch": _colour(rgb, masks_np), "final_seg_sketch": _colour(rgb, final_masks),
+    return {"initial_seg_sketch": _colour(rgb, masks_np),
+            "final_seg_sketch": Image.fromarray(_colour_labels(rgb, final, len(masks_np), extra)),
             "final_masks": final_masks}
 
 
@@ -120,8 +132,8 @@ def run_refinement_on_sketch_dir(sketch_dir, bboxes_path, out_base_dir=None, cle
     depth_map = depth_dev.cpu().numpy()
     lo, hi = float(depth_map.min()), float(depth_map.max())             # cv2.normalize(NORM_MINMAX, 0..255)
     norm = (depth_map - lo) * (255.0 / (hi - lo)) if hi > lo else np.zeros_like(depth_map)
-    from InkLayer.runner import colour_by_masks
+    coloured = _colour_labels(rgb, res.final, res.n_disjoint, res.extra)     # refiner.py:360-362, from the final label image
     save_all([(lambda: np.repeat(np.clip(norm, 0, 255).astype(np.uint8)[..., None], 3, axis=2), f"{out_base_dir}/depth_map.png"),
-              (lambda: colour_by_masks(rgb, final_masks), f"{out_base_dir}/segmented_sketch_final.png")], wait=None)
+              (coloured, f"{out_base_dir}/segmented_sketch_final.png")], wait=None)
     print(f"Results saved to {out_dir}")
     return out_dir

@@ -15,32 +15,7 @@ from InkLayer.detector.gdino import run_ft_dino_on_sketch
 from InkLayer.segmentor.sam import run_SAM
 from InkLayer.utils.io import flush, save_all
 from InkLayer.utils.processing import process_dino_output, save_norm_bboxes
-
-
-def _draw_boxes(input_pil, boxes):
-    im = input_pil.copy()
-    d = ImageDraw.Draw(im)
-    for b in boxes:
-        d.rectangle([b[0], b[1], b[2], b[3]], outline=(220, 40, 40), width=2)
-    return im
-
-
-def colour_by_masks(rgb, masks):
-    """A plain visualisation (InkLayer/utils/visualization.py is outside the hot path): every mask tints its pixels
-    half / half with its own colour, later masks on top.  One label image + one table look-up in uint8 instead of a
-    float pass over the image per mask.  rgb: uint8 [H, W, 3]; masks: sequence of [H, W] arrays (non-zero = inside)."""
-    import numpy as np
-    base = np.asarray(rgb)
-    label = np.zeros(base.shape[:2], np.uint16)
-    half = np.zeros((len(masks) + 1, 3), np.uint8)
-    for i, m in enumerate(masks):
-        hue = (i * 0.61803398875) % 1.0
-        half[i + 1] = [int(127.5 * (0.6 + 0.4 * abs(((hue * 6 + k) % 6) / 3 - 1))) for k in (0, 4, 2)]
-        label[np.asarray(m) != 0] = i + 1
-    out = base.copy()
-    sel = label > 0
-    out[sel] = (base[sel] >> 1) + half[label[sel]]
-    return out
+from InkLayer.utils.visualization import draw_norm_bbox_on_image
 
 
 def _prepare_out_dir(input_path, out_base_dir, wait=True):
@@ -92,9 +67,16 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
         masks_dir = os.path.join(out_dir, "masks")
         os.makedirs(masks_dir, exist_ok=True)
         rgb = np.asarray(input_pil)
+        # segmented_sketch.png (runner.py:52): the kernels are launched here, on the caller's thread and stream, from the
+        # masks still in HBM when the caller has them; the I/O threads only get the finished host array
+        from inklayer_amd.visualize import colour_sketch
+        coloured = colour_sketch(rgb, masks_dev if masks_dev is not None and len(masks_np) else masks_np)
+        if hasattr(coloured, "cpu"):
+            coloured = coloured.cpu().numpy()
         save_all([(np.asarray(m, dtype=bool), os.path.join(masks_dir, f"mask_{i}.png")) for i, m in enumerate(masks_np)]  # 1-bit, PIL mode "1"
-                 + [(lambda: colour_by_masks(rgb, masks_np), os.path.join(out_dir, "segmented_sketch.png")),
-                    (lambda: _draw_boxes(input_pil, boxes_int), os.path.join(out_dir, "bboxes.png"))], wait=False)
+                 + [(coloured, os.path.join(out_dir, "segmented_sketch.png")),
+                    (lambda: draw_norm_bbox_on_image(input_pil, boxes_int, dino_out.get("labels")), os.path.join(out_dir, "bboxes.png"))],
+                 wait=False)
         _tick("masks/ + detection visualisations (files)", t0)
         t0 = time.perf_counter()
 

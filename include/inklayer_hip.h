@@ -753,6 +753,28 @@ int ink_inp_unsharp(const void* img_u8, int32_t H, int32_t W, int32_t channels, 
 /* The RGBA layer of inpaint_single_layer.py:74-78: the result with alpha 255 where mask > 128, zeros elsewhere. */
 int ink_inp_rgba_cut(const void* rgb_u8, const void* mask_u8, int32_t H, int32_t W, void* rgba_u8, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Visualisation: the coloured sketch (csrc/visualize.hip).  The sketch is uint8 [H, W, 3] (R, G, B;
+ * channels 3) or uint8 [H, W] (channels 1), grey = cv2.cvtColor(COLOR_RGB2GRAY) = (4899 R + 9617 G + 1868 B + 8192)
+ * >> 14, or the single channel as it is (InkLayer/utils/visualization.py:79-85).  No pointer needs any alignment.
+ * ------------------------------------------------------------------------ */
+
+/* *gray_min = the smallest grey over the stroke pixels (grey < 250, visualization.py:92), 0x7f7f7f7f when the image has
+ * none.  The word is reset on the stream before the kernel, so one buffer serves call after call; the host never
+ * reads it: ink_vis_colour takes it from the device (max_stroke_opacity > 0.1, visualization.py:103-109, <=> it is
+ * <= 229). */
+int ink_vis_gray_min(const void* sketch_u8, int32_t channels, int32_t H, int32_t W, int32_t* gray_min, void* stream);
+
+/* color_sketch_by_masks (visualization.py:63-167) as a table look-up: out uint8 [H, W, 3] = white where grey >= 250
+ * (whatever the masks say), else tables[v][row][grey] with v = 0 when *gray_min <= 229 (power-law opacity, :109-118)
+ * and 1 otherwise (:119-125), row = the index of the LAST mask holding the pixel (:131-150) or n for a stroke in no
+ * mask (:152-165, 169-180).  by_label == 0: masks_or_label = uint8 [n, H, W], non-zero = inside (may be null when
+ * n == 0); by_label != 0: uint8 [H, W], 0 = no mask, l = mask l - 1, a label above n counts as 0, n <= 255.
+ * tables: uint8 [2, n + 1, 256, 3], built on the host (inklayer_amd/visualize.py::colour_tables). */
+int ink_vis_colour(const void* sketch_u8, int32_t channels, const void* masks_or_label_u8, int32_t n, int32_t by_label,
+                   const void* tables_u8, const int32_t* gray_min, int32_t H, int32_t W, void* out_rgb_u8,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

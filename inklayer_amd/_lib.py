@@ -159,6 +159,8 @@ SIGNATURES = {
     "ink_inp_luma": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_inp_unsharp": [c_void_p, c_int, c_int, c_int, C.c_uint32, C.c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_inp_rgba_cut": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "ink_vis_gray_min": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_vis_colour": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_relpos_bias": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }

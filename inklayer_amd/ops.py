@@ -1249,6 +1249,46 @@ def layers_rgba(gray_u8: torch.Tensor, bg_planes: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+# Visualisation: the coloured sketch (csrc/visualize.hip)
+# ---------------------------------------------------------------------------------------------
+def _check_sketch(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), f"{what}: contiguous uint8 CUDA tensor expected"
+    assert t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3), f"{what}: sketch [H, W, 3] or [H, W] expected"
+    return (1 if t.dim() == 2 else 3), int(t.shape[0]), int(t.shape[1])
+
+
+def vis_gray_min(sketch_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [1] on the device: the smallest grey over the stroke pixels (grey < 250) of the sketch, 0x7f7f7f7f when it
+    has none.  `out`: a buffer to reuse (it is reset on the stream)."""
+    ch, H, W = _check_sketch(sketch_u8, "vis_gray_min")
+    if out is None:
+        out = torch.empty(1, device=sketch_u8.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and out.is_cuda and out.numel() == 1
+    check(_lib.lib().ink_vis_gray_min(sketch_u8.data_ptr(), ch, H, W, out.data_ptr(), _stream()), "ink_vis_gray_min")
+    return out
+
+
+def vis_colour(sketch_u8: torch.Tensor, masks_or_label_u8: torch.Tensor, tables_u8: torch.Tensor, gray_min: torch.Tensor,
+               by_label: bool = False) -> torch.Tensor:
+    """color_sketch_by_masks -> uint8 [H, W, 3].  masks_or_label_u8: the masks [n, H, W] (non-zero = inside, the last one
+    holding a pixel wins) or, by_label, the label image [H, W]; tables_u8: [2, n + 1, 256, 3] from
+    visualize.colour_tables; gray_min: what vis_gray_min returned for this sketch."""
+    ch, H, W = _check_sketch(sketch_u8, "vis_colour")
+    m = masks_or_label_u8
+    assert m.dtype == torch.uint8 and m.is_cuda and m.is_contiguous(), "vis_colour: contiguous uint8 CUDA masks expected"
+    assert tables_u8.dtype == torch.uint8 and tables_u8.is_cuda and tables_u8.is_contiguous() and tables_u8.dim() == 4
+    n = int(tables_u8.shape[1]) - 1
+    assert tuple(tables_u8.shape) == (2, n + 1, 256, 3)
+    assert tuple(m.shape) == ((H, W) if by_label else (n, H, W)), "vis_colour: masks / label image do not fit the tables"
+    assert gray_min.dtype == torch.int32 and gray_min.is_cuda and gray_min.numel() == 1
+    out = torch.empty((H, W, 3), device=sketch_u8.device, dtype=torch.uint8)
+    check(_lib.lib().ink_vis_colour(sketch_u8.data_ptr(), ch, m.data_ptr() if m.numel() else None, n, int(bool(by_label)),
+                                    tables_u8.data_ptr(), gray_min.data_ptr(), H, W, out.data_ptr(), _stream()),
+          "ink_vis_colour")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Inpainting pre- and post-processing (DESIGN §9, csrc/inpaint_ops.hip): uint8 [H, W, 3] (R, G, B) and uint8 [H, W]
 # ---------------------------------------------------------------------------------------------
 def _check_img(t: torch.Tensor, channels: int, what: str) -> Tuple[int, int]:
