@@ -1,6 +1,6 @@
 """bench.py — sketches/sec end-to-end (GroundingDINO Swin-T + SAM ViT-H) at 1024x1024 on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N)
     or directly - bench.py then starts its N ranks itself (fresh child processes, before anything touches the GPU).
 
@@ -12,10 +12,15 @@ random weights) -> SAM encoder (B images) -> prompt encoder + mask decoder + pos
 B x 16 uint8 0/1 masks of 1024x1024 downloaded into pinned host memory (1 byte per pixel, the reference's numpy bool
 format; 134 MB per step), boxes/scores on the host.  Uploads and downloads ride a copy stream and overlap with the
 neighbouring step's compute (two slots); every one of the K timed steps is complete - masks in host memory - when the
-clock stops.  `device_resident` repeats the measurement without the PCIe legs (round 1's number).
+clock stops.
 Image-parallel over ranks (weak scaling), one RCCL weight broadcast at start-up, no per-batch collectives.
 Prints ONE JSON line on rank 0; its `ms_per_step` is the wall time of one of the K timed steps.  --dump-outputs DIR
 also writes what the last timed step returned as DIR/*.npy (see dump_outputs).
+A plain run does no more than that: set-up, W warm-up steps, the K timed steps, the dump, the line.  --full adds, after
+the timed region and in the same JSON line, everything else the benchmark measures or checks (full_figures): the last
+timed step against one synchronous step, `device_resident` (the measurement repeated without the PCIe legs, round 1's
+number), the roofline and attention figures, and on one GPU the whole runner and the CPU baseline (--no-runner and
+--no-cpu-baseline leave those two out).
 """
 import argparse
 import json
@@ -244,6 +249,117 @@ def attention_summary(trace, steps):
     return out
 
 
+def full_figures(args, pipe, det, seg, imgs, host, res, rank, world, dev, dt):
+    """--full: everything the benchmark measures or checks besides its headline figure, run after the timed region
+    (and after --dump-outputs, since the check step reuses the pinned host buffers).  Every rank takes part in the
+    collective parts; rank 0 returns the extra keys of the JSON line, the other ranks None."""
+    from inklayer_amd import dist as idist, ops, pipeline
+    B = args.batch
+    sketches = B * world * args.steps
+    # the LAST timed step (submitted with its predecessor still in flight) against one synchronous step: same bytes?
+    # (round 3: kernels co-resident with the window-attention kernel returned wrong results in a third of in-flight steps
+    # until that kernel claimed its SIMDs' register file - DESIGN.md section 7; the bench now says so if it ever recurs)
+    timed_boxes = [np.array(r[0], copy=True) for r in res]
+    timed_sum = [int(r[3].sum(dtype=np.int64)) for r in res]
+    torch.cuda.synchronize()
+    chk = pipe.collect_host(pipe.submit_host(host, top_n=args.boxes))
+    verified = all(np.array_equal(a, r[0]) and sa == int(r[3].sum(dtype=np.int64))
+                   for a, sa, r in zip(timed_boxes, timed_sum, chk))
+
+    # secondary figure: the same steps with inputs and outputs resident in HBM (no PCIe legs)
+    raw = pipe.upload(imgs)
+    torch.cuda.synchronize()
+    idist.barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        pipe.run_uploaded(raw, top_n=args.boxes)
+    torch.cuda.synchronize()
+    idist.barrier()
+    dt_dev = idist.max_over_ranks(time.perf_counter() - t0, dev)
+
+    # Roofline instrumentation: the same steps once more with every GEMM / attention launch bracketed by HIP events on
+    # its launch stream, in SERIAL stream order (detector, then SAM) so that the events time the kernel itself and not
+    # the co-scheduling delay of the two-stream overlap (which the timed region uses).
+    trace, atrace = [], []
+    roof_steps = min(2, args.steps)
+    if rank == 0:
+        serial = pipeline.InkLayerPipeline(det, seg, overlap=False)
+        ops.set_gemm_trace(trace)
+        ops.set_attn_trace(atrace)
+        for _ in range(roof_steps):
+            serial.run_uploaded(raw, top_n=args.boxes)
+        torch.cuda.synchronize()
+        ops.set_gemm_trace(None)
+        ops.set_attn_trace(None)
+        # ... and once in the two-stream arrangement of the timed region: there a launch's bracket also contains the time
+        # its workgroups wait for CUs held by the other stream's kernels - what a rocprofv3 --stats average over this
+        # whole command mostly consists of (reported as avg_launch_us_two_streams, not used for `frac`)
+        trace2 = []
+        ops.set_gemm_trace(trace2)
+        for _ in range(roof_steps):
+            pipe.run_uploaded(raw, top_n=args.boxes)
+        torch.cuda.synchronize()
+        ops.set_gemm_trace(None)
+
+    extra = None
+    if rank == 0:
+        from inklayer_amd import _lib
+        gemm_ms = sum(t[1].elapsed_time(t[2]) for t in trace)
+        gemm_flops = sum(t[0] for t in trace)
+        # the dominant kernel = the tile variant with the largest total time: its launches, flops, bytes, durations
+        names = {45: "gemm_f16_nt_pp<4,5> (ping-pong 256x320x32 tile, 8 waves: dense projections of SAM ViT-H)",
+                 10: "gemm_f16_nt<256,256,64,4,4,2> (16-wave 256x256 tile: DINO FFN and other large projections)",
+                 0: "gemm_f16_nt<128,128,64,2,2,2>", 32: "gemm_f16_nt<128,128,32,2,2,2>"}
+        by_var = {}
+        for t in trace:
+            by_var.setdefault(_lib.lib().ink_gemm_query_variant(t[3][0], t[3][1], t[3][2]), []).append(t)
+        dom_var = max(by_var, key=lambda v: sum(t[1].elapsed_time(t[2]) for t in by_var[v]))
+        dom = by_var[dom_var]
+        traffic = None
+        pmcs = sorted((ROOT / "profiles").glob("r*_gemm_pmc.json"))     # the newest round's counters
+        pmc = pmcs[-1] if pmcs else ROOT / "profiles" / "none"
+        if pmc.exists():      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command (see DESIGN.md §7)
+            pj = json.loads(pmc.read_text())
+            if pj.get("variant") == dom_var:
+                traffic = pj.get("traffic_bytes_per_launch")
+        dom_ms = sum(t[1].elapsed_time(t[2]) for t in dom)
+        dom_flops = sum(t[0] for t in dom)
+        abytes = lambda k: (2.0 * (k[0] * k[2] + k[1] * k[2])                       # A + W in f16
+                            + k[0] * k[1] * ((2 if k[6] == "f16" else 4) + (4 if k[4] == "res" else 0)))  # C (+ residual)
+        dom_bytes = sum(abytes(t[3]) for t in dom)
+        achieved = dom_flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+        extra = {
+            "timed_step_equals_synchronous_step": bool(verified),
+            "device_resident": {"value": sketches / dt_dev, "unit": "sketches/s", "ms_per_step": dt_dev / args.steps * 1e3,
+                                "note": "same steps with sketches and masks left in HBM (no PCIe legs); not the metric"},
+            "roofline": {"bound": "mfma", "kernel": names.get(dom_var, str(dom_var)),
+                         "achieved": achieved, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved / PEAK_F16_TFLOPS, "traffic": traffic,
+                         "traffic_unit": "HBM-side bytes per launch (2*FETCH_SIZE + WRITE_SIZE, rocprofv3 --pmc)",
+                         "algorithmic_bytes_per_launch": dom_bytes / max(1, len(dom)),
+                         "algorithmic_flop_per_launch": dom_flops / max(1, len(dom)),
+                         "avg_launch_us": dom_ms * 1e3 / max(1, len(dom)),
+                         "avg_launch_us_two_streams": (lambda d2: sum(t[1].elapsed_time(t[2]) for t in d2) * 1e3 / max(1, len(d2)))(
+                             [t for t in trace2 if _lib.lib().ink_gemm_query_variant(t[3][0], t[3][1], t[3][2]) == dom_var]),
+                         "launches_per_step": len(dom) // max(1, roof_steps),
+                         "ms_per_step": dom_ms / max(1, roof_steps),
+                         "all_gemm_launches_per_step": len(trace) // max(1, roof_steps),
+                         "all_gemm_ms_per_step": gemm_ms / max(1, roof_steps),
+                         "gemm_tflop_per_sketch": gemm_flops / max(1, roof_steps) / B / 1e12,
+                         "note": "HIP-event brackets per launch over %d extra steps run in serial stream order right after "
+                                 "the timed region (the timed region overlaps detector and SAM encoder on two streams)" % roof_steps,
+                         "end_to_end_tflops": FLOP_PER_SKETCH * sketches / dt / 1e12 / world},
+            "attention": attention_summary(atrace, roof_steps),
+        }
+        if world == 1 and not args.no_runner:
+            import contextlib
+            with contextlib.redirect_stdout(sys.stderr):     # the runner prints the reference's progress lines: the
+                extra["runner"] = runner_leg(pipe, args.batch, args.boxes)   # bench's stdout is ONE JSON line
+        if world == 1 and not args.no_cpu_baseline:
+            extra["cpu_baseline"] = cpu_baseline(args.boxes)
+    return extra
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -251,8 +367,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="sketches per GPU per step")
     ap.add_argument("--boxes", type=int, default=16, help="boxes per sketch (top-n by score)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-runner", action="store_true", help="skip the secondary whole-runner (config 5) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the "
+                         "synchronous check step, device-resident steps, roofline and attention figures, the whole "
+                         "runner and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-runner", action="store_true",
+                    help="with --full: skip the secondary whole-runner (config 5) measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (rank 0's sketches) to DIR/<name>.npy")
     args = ap.parse_args()
@@ -268,7 +389,7 @@ def main():
             print(line, file=sys.stdout if line.startswith("{") else sys.stderr, flush=True)
         sys.exit(rc)
 
-    from inklayer_amd import ops, pipeline, synthetic
+    from inklayer_amd import pipeline, synthetic
     rank, world, local = idist.init_process_group()
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     torch.cuda.set_device(local)
@@ -305,77 +426,9 @@ def main():
     assert len(res) == B and res[0][3].shape == (args.boxes, 1024, 1024) and res[0][3].dtype == np.uint8
     if args.dump_outputs and rank == 0:      # before the check step below reuses the pinned host buffers
         dump_outputs(res, args.dump_outputs)
-    # the LAST timed step (submitted with its predecessor still in flight) against one synchronous step: same bytes?
-    # (round 3: kernels co-resident with the window-attention kernel returned wrong results in a third of in-flight steps
-    # until that kernel claimed its SIMDs' register file - DESIGN.md section 7; the bench now says so if it ever recurs)
-    timed_boxes = [np.array(r[0], copy=True) for r in res]
-    timed_sum = [int(r[3].sum(dtype=np.int64)) for r in res]
-    torch.cuda.synchronize()
-    chk = pipe.collect_host(pipe.submit_host(host, top_n=args.boxes))
-    verified = all(np.array_equal(a, r[0]) and sa == int(r[3].sum(dtype=np.int64))
-                   for a, sa, r in zip(timed_boxes, timed_sum, chk))
-
-    # secondary figure: the same steps with inputs and outputs resident in HBM (no PCIe legs)
-    raw = pipe.upload(imgs)
-    torch.cuda.synchronize()
-    idist.barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        pipe.run_uploaded(raw, top_n=args.boxes)
-    torch.cuda.synchronize()
-    idist.barrier()
-    dt_dev = idist.max_over_ranks(time.perf_counter() - t0, dev)
-
-    # Roofline instrumentation: the same steps once more with every GEMM / attention launch bracketed by HIP events on
-    # its launch stream, in SERIAL stream order (detector, then SAM) so that the events time the kernel itself and not
-    # the co-scheduling delay of the two-stream overlap (which the timed region above uses).
-    trace, atrace = [], []
-    roof_steps = min(2, args.steps)
-    if rank == 0:
-        serial = pipeline.InkLayerPipeline(det, seg, overlap=False)
-        ops.set_gemm_trace(trace)
-        ops.set_attn_trace(atrace)
-        for _ in range(roof_steps):
-            serial.run_uploaded(raw, top_n=args.boxes)
-        torch.cuda.synchronize()
-        ops.set_gemm_trace(None)
-        ops.set_attn_trace(None)
-        # ... and once in the two-stream arrangement of the timed region: there a launch's bracket also contains the time
-        # its workgroups wait for CUs held by the other stream's kernels - what a rocprofv3 --stats average over this
-        # whole command mostly consists of (reported as avg_launch_us_two_streams, not used for `frac`)
-        trace2 = []
-        ops.set_gemm_trace(trace2)
-        for _ in range(roof_steps):
-            pipe.run_uploaded(raw, top_n=args.boxes)
-        torch.cuda.synchronize()
-        ops.set_gemm_trace(None)
+    extra = full_figures(args, pipe, det, seg, imgs, host, res, rank, world, dev, dt) if args.full else None
 
     if rank == 0:
-        from inklayer_amd import _lib
-        gemm_ms = sum(t[1].elapsed_time(t[2]) for t in trace)
-        gemm_flops = sum(t[0] for t in trace)
-        # the dominant kernel = the tile variant with the largest total time: its launches, flops, bytes, durations
-        names = {45: "gemm_f16_nt_pp<4,5> (ping-pong 256x320x32 tile, 8 waves: dense projections of SAM ViT-H)",
-                 10: "gemm_f16_nt<256,256,64,4,4,2> (16-wave 256x256 tile: DINO FFN and other large projections)",
-                 0: "gemm_f16_nt<128,128,64,2,2,2>", 32: "gemm_f16_nt<128,128,32,2,2,2>"}
-        by_var = {}
-        for t in trace:
-            by_var.setdefault(_lib.lib().ink_gemm_query_variant(t[3][0], t[3][1], t[3][2]), []).append(t)
-        dom_var = max(by_var, key=lambda v: sum(t[1].elapsed_time(t[2]) for t in by_var[v]))
-        dom = by_var[dom_var]
-        traffic = None
-        pmcs = sorted((ROOT / "profiles").glob("r*_gemm_pmc.json"))     # the newest round's counters
-        pmc = pmcs[-1] if pmcs else ROOT / "profiles" / "none"
-        if pmc.exists():      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
-            pj = json.loads(pmc.read_text())
-            if pj.get("variant") == dom_var:
-                traffic = pj.get("traffic_bytes_per_launch")
-        dom_ms = sum(t[1].elapsed_time(t[2]) for t in dom)
-        dom_flops = sum(t[0] for t in dom)
-        abytes = lambda k: (2.0 * (k[0] * k[2] + k[1] * k[2])                       # A + W in f16
-                            + k[0] * k[1] * ((2 if k[6] == "f16" else 4) + (4 if k[4] == "res" else 0)))  # C (+ residual)
-        dom_bytes = sum(abytes(t[3]) for t in dom)
-        achieved = dom_flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
         sketches = B * world * args.steps
         out = {
             "metric": "sketches/sec end-to-end (GroundingDINO+SAM) at 1024x1024",
@@ -385,40 +438,15 @@ def main():
             "dtype": "f16 (MFMA, f32 accumulate; f32 residual/norm/softmax; split-f16 = fp32-grade operands for "
                      "patch-embed, neck, mask decoder)",
             "data": "synthetic",
-            "timed_step_equals_synchronous_step": bool(verified),
             "config": {"workload": "full GroundingDINO Swin-T + SAM ViT-H pipeline, batch=8 per GPU, "
                                    "1024x1024 synthetic sketches, 16 boxes/sketch, random-init weights",
                        "global_batch": B * world, "boxes_per_sketch": args.boxes,
                        "parallelism": f"image-parallel x{world}", "weight_broadcast_s": round(bcast_s, 3),
                        "timed_region": "host to host: pinned u8 sketches -> H2D -> pipeline -> D2H of u8 masks (1 B/pixel, "
                                        "134 MB/step at batch 8) + boxes; copies on a copy stream, 2 slots"},
-            "device_resident": {"value": sketches / dt_dev, "unit": "sketches/s", "ms_per_step": dt_dev / args.steps * 1e3,
-                                "note": "same steps with sketches and masks left in HBM (no PCIe legs); not the metric"},
-            "roofline": {"bound": "mfma", "kernel": names.get(dom_var, str(dom_var)),
-                         "achieved": achieved, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_F16_TFLOPS, "traffic": traffic,
-                         "traffic_unit": "HBM-side bytes per launch (2*FETCH_SIZE + WRITE_SIZE, rocprofv3 --pmc)",
-                         "algorithmic_bytes_per_launch": dom_bytes / max(1, len(dom)),
-                         "algorithmic_flop_per_launch": dom_flops / max(1, len(dom)),
-                         "avg_launch_us": dom_ms * 1e3 / max(1, len(dom)),
-                         "avg_launch_us_two_streams": (lambda d2: sum(t[1].elapsed_time(t[2]) for t in d2) * 1e3 / max(1, len(d2)))(
-                             [t for t in trace2 if _lib.lib().ink_gemm_query_variant(t[3][0], t[3][1], t[3][2]) == dom_var]),
-                         "launches_per_step": len(dom) // max(1, roof_steps),
-                         "ms_per_step": dom_ms / max(1, roof_steps),
-                         "all_gemm_launches_per_step": len(trace) // max(1, roof_steps),
-                         "all_gemm_ms_per_step": gemm_ms / max(1, roof_steps),
-                         "gemm_tflop_per_sketch": gemm_flops / max(1, roof_steps) / B / 1e12,
-                         "note": "HIP-event brackets per launch over %d extra steps run in serial stream order right after "
-                                 "the timed region (the timed region overlaps detector and SAM encoder on two streams)" % roof_steps,
-                         "end_to_end_tflops": FLOP_PER_SKETCH * sketches / dt / 1e12 / world},
-            "attention": attention_summary(atrace, roof_steps),
         }
-        if world == 1 and not args.no_runner:
-            import contextlib
-            with contextlib.redirect_stdout(sys.stderr):     # the runner prints the reference's progress lines: the
-                out["runner"] = runner_leg(pipe, args.batch, args.boxes)   # bench's stdout is ONE JSON line
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.boxes)
+        if extra:
+            out.update(extra)
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
