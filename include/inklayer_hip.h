@@ -775,6 +775,39 @@ int ink_vis_colour(const void* sketch_u8, int32_t channels, const void* masks_or
                    const void* tables_u8, const int32_t* gray_min, int32_t H, int32_t W, void* out_rgb_u8,
                    void* stream);
 
+/* ------------------------------------------------------------------------
+ * Evaluation: counting predictions against a ground-truth label image (csrc/evaluate.hip).  All results are
+ * integers and do not depend on the order of the pixels.  H W < 2^31; no pointer needs more than its element's
+ * alignment (the byte images none).  Every output is cleared on the stream by the call itself.
+ * ------------------------------------------------------------------------ */
+
+/* The distinct values of a label image and each pixel's index among them.  labels: [H, W] of elem_size 1 (uint8), 2
+ * (uint16) or 4 (int32) bytes, values 0 .. 65535.  workspace: 4096 uint32 (presence bitmap and its word prefix counts).
+ * info[0] = U, the number of distinct values; info[1] != 0 when some value is negative or above 65535 (such a pixel gets
+ * rank 0 and the results are not to be used).  values: the sorted table, the first min(U, values_cap) entries.
+ * rank: uint16 [H, W], rank[y, x] = index of labels[y, x] in the table. */
+int ink_eval_label_ranks(const void* labels, int32_t elem_size, int32_t H, int32_t W, uint32_t* workspace,
+                         int32_t* values, int32_t values_cap, int32_t* info, uint16_t* rank, void* stream);
+
+/* table int32 [n + 1, U]: table[i, u] = number of counted pixels inside prediction i whose rank is u; row n counts every
+ * counted pixel (the ground-truth areas).  by_label == 0: pred_u8 = uint8 [n, H, W], non-zero = inside, masks may overlap
+ * (may be null when n == 0); by_label != 0: uint8 [H, W], l = mask l - 1, 0 and labels above n = no mask, n <= 255.
+ * 1 <= U <= 256; a pixel whose rank is >= U is left out.  stroke_only != 0: only pixels whose grey is below 250 count,
+ * sketch_u8 = uint8 [H, W, 3] (R, G, B; channels 3, grey as ink_vis_gray_min) or [H, W] (channels 1); otherwise the
+ * sketch is not read. */
+int ink_eval_contingency(const void* pred_u8, int32_t n, int32_t by_label, const void* rank_u16, int32_t U,
+                         const void* sketch_u8, int32_t channels, int32_t stroke_only, int32_t H, int32_t W,
+                         int32_t* table, void* stream);
+
+/* boxes int32 [U, 4]: xmin, ymin, xmax, ymax (inclusive) of the pixels of every rank; (INT_MAX, INT_MAX, -1, -1) for a
+ * rank without pixels.  1 <= U <= 256. */
+int ink_eval_label_boxes(const void* rank_u16, int32_t U, int32_t H, int32_t W, int32_t* boxes, void* stream);
+
+/* out uint8 [H, W, 3] = colors[rank] with colors uint8 [U, 3] (white for a rank >= U): the ground-truth picture of
+ * InkScenes/read_GT_mat_file.py:40-70.  1 <= U <= 256. */
+int ink_eval_paint_labels(const void* rank_u16, const void* colors_u8, int32_t U, int32_t H, int32_t W, void* out_rgb_u8,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

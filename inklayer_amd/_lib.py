@@ -161,6 +161,11 @@ SIGNATURES = {
     "ink_inp_rgba_cut": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_vis_gray_min": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_vis_colour": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "ink_eval_label_ranks": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_eval_contingency": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                             c_void_p],
+    "ink_eval_label_boxes": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_eval_paint_labels": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_relpos_bias": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }

@@ -1289,6 +1289,80 @@ def vis_colour(sketch_u8: torch.Tensor, masks_or_label_u8: torch.Tensor, tables_
 
 
 # ---------------------------------------------------------------------------------------------
+# Evaluation: counting predictions against a ground-truth label image (csrc/evaluate.hip)
+# ---------------------------------------------------------------------------------------------
+EVAL_MAX_VALUES = 256       # columns of a contingency table (csrc/evaluate.hip EVAL_MAX_U)
+_EVAL_ELEM = {torch.uint8: 1, torch.uint16: 2, torch.int32: 4}
+
+
+def _check_rank(rank_u16: torch.Tensor, what: str) -> Tuple[int, int]:
+    assert rank_u16.dtype == torch.uint16 and rank_u16.is_cuda and rank_u16.is_contiguous() and rank_u16.dim() == 2, \
+        f"{what}: contiguous uint16 CUDA rank image [H, W] expected"
+    return int(rank_u16.shape[0]), int(rank_u16.shape[1])
+
+
+def eval_label_ranks(labels: torch.Tensor, values_cap: int = EVAL_MAX_VALUES):
+    """-> (rank uint16 [H, W], values int32 [values_cap], info int32 [2]), all on the device: values[:U] = the sorted
+    distinct values of the label image (uint8, uint16 or int32, 0 .. 65535), rank = each pixel's index among them,
+    info = (U, error flag: some value negative or above 65535).  The caller reads `info` (one synchronisation)."""
+    assert labels.dtype in _EVAL_ELEM and labels.is_cuda and labels.is_contiguous() and labels.dim() == 2, \
+        "eval_label_ranks: contiguous uint8 / uint16 / int32 CUDA label image [H, W] expected"
+    H, W = (int(v) for v in labels.shape)
+    dev = labels.device
+    work = torch.empty(4096, device=dev, dtype=torch.int32)
+    values = torch.zeros(int(values_cap), device=dev, dtype=torch.int32)
+    info = torch.empty(2, device=dev, dtype=torch.int32)
+    rank = torch.empty((H, W), device=dev, dtype=torch.uint16)
+    check(_lib.lib().ink_eval_label_ranks(labels.data_ptr(), _EVAL_ELEM[labels.dtype], H, W, work.data_ptr(),
+                                          values.data_ptr(), int(values_cap), info.data_ptr(), rank.data_ptr(), _stream()),
+          "ink_eval_label_ranks")
+    return rank, values, info
+
+
+def eval_contingency(pred_u8: torch.Tensor, rank_u16: torch.Tensor, n_values: int, n_labels: Optional[int] = None,
+                     sketch_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> int32 [n + 1, n_values]: [i, u] = pixels inside prediction i with ground-truth rank u, row n = every counted
+    pixel.  pred_u8: the masks [n, H, W] (non-zero = inside) or, with n_labels = n given, a label image [H, W] (l = mask
+    l - 1).  sketch_u8 given: only its stroke pixels (grey < 250) count."""
+    H, W = _check_rank(rank_u16, "eval_contingency")
+    by_label = n_labels is not None
+    assert pred_u8.dtype == torch.uint8 and pred_u8.is_cuda and pred_u8.is_contiguous(), \
+        "eval_contingency: contiguous uint8 CUDA predictions expected"
+    n = int(n_labels) if by_label else int(pred_u8.shape[0])
+    assert tuple(pred_u8.shape) == ((H, W) if by_label else (n, H, W)), "eval_contingency: predictions do not fit the rank image"
+    ch = 1
+    if sketch_u8 is not None:
+        ch, sh, sw = _check_sketch(sketch_u8, "eval_contingency")
+        assert (sh, sw) == (H, W), "eval_contingency: sketch does not fit the rank image"
+    table = torch.empty((n + 1, int(n_values)), device=rank_u16.device, dtype=torch.int32)
+    check(_lib.lib().ink_eval_contingency(pred_u8.data_ptr() if pred_u8.numel() else None, n, int(by_label), rank_u16.data_ptr(),
+                                          int(n_values), None if sketch_u8 is None else sketch_u8.data_ptr(), ch,
+                                          int(sketch_u8 is not None), H, W, table.data_ptr(), _stream()),
+          "ink_eval_contingency")
+    return table
+
+
+def eval_label_boxes(rank_u16: torch.Tensor, n_values: int) -> torch.Tensor:
+    """-> int32 [n_values, 4]: xmin, ymin, xmax, ymax (inclusive) of the pixels of every rank."""
+    H, W = _check_rank(rank_u16, "eval_label_boxes")
+    boxes = torch.empty((int(n_values), 4), device=rank_u16.device, dtype=torch.int32)
+    check(_lib.lib().ink_eval_label_boxes(rank_u16.data_ptr(), int(n_values), H, W, boxes.data_ptr(), _stream()),
+          "ink_eval_label_boxes")
+    return boxes
+
+
+def eval_paint_labels(rank_u16: torch.Tensor, colors_u8: torch.Tensor) -> torch.Tensor:
+    """-> uint8 [H, W, 3]: colors_u8 [U, 3] looked up by rank."""
+    H, W = _check_rank(rank_u16, "eval_paint_labels")
+    assert colors_u8.dtype == torch.uint8 and colors_u8.is_cuda and colors_u8.is_contiguous() and colors_u8.dim() == 2 \
+        and colors_u8.shape[1] == 3, "eval_paint_labels: contiguous uint8 CUDA colours [U, 3] expected"
+    out = torch.empty((H, W, 3), device=rank_u16.device, dtype=torch.uint8)
+    check(_lib.lib().ink_eval_paint_labels(rank_u16.data_ptr(), colors_u8.data_ptr(), int(colors_u8.shape[0]), H, W,
+                                           out.data_ptr(), _stream()), "ink_eval_paint_labels")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Inpainting pre- and post-processing (DESIGN §9, csrc/inpaint_ops.hip): uint8 [H, W, 3] (R, G, B) and uint8 [H, W]
 # ---------------------------------------------------------------------------------------------
 def _check_img(t: torch.Tensor, channels: int, what: str) -> Tuple[int, int]:
