@@ -444,7 +444,7 @@ extern "C" int ink_refine_depth_samples(const void* mask_planes, int32_t n, cons
 extern "C" int ink_refine_pair_tables(const void* mask_planes, const void* sketch_planes4, int32_t n, int32_t H,
                                       int32_t W, const int32_t* rect, void* dil_ws_planes, int32_t* pair,
                                       int32_t* per_mask, int32_t* sketch_area, void* stream) {
-  INK_CHECK_ARG(sketch_planes4 && sketch_area && n >= 0 && H > 0 && W > 0);
+  INK_CHECK_ARG(sketch_planes4 && sketch_area && n >= 0 && H > 0 && W > 0 && H <= 16383 && W <= 16383);
   INK_CHECK_ARG(n == 0 || (mask_planes && rect && dil_ws_planes && pair && per_mask));
   hipStream_t s = (hipStream_t)stream;
   const int Wp = (W + 63) / 64;
@@ -464,7 +464,7 @@ extern "C" int ink_refine_pair_tables(const void* mask_planes, const void* sketc
 
 extern "C" int ink_refine_composite(const void* mask_planes, const int32_t* order, int32_t n_ranks, int32_t H, int32_t W,
                                     void* label_u8, int32_t* hist256, void* stream) {
-  INK_CHECK_ARG(label_u8 && hist256 && H > 0 && W > 0 && n_ranks >= 0 && n_ranks <= 254);
+  INK_CHECK_ARG(label_u8 && hist256 && H > 0 && W > 0 && H <= 16383 && W <= 16383 && n_ranks >= 0 && n_ranks <= 254);
   INK_CHECK_ARG(n_ranks == 0 || (mask_planes && order));
   hipStream_t s = (hipStream_t)stream;
   const int Wp = (W + 63) / 64;
@@ -542,8 +542,8 @@ extern "C" int ink_refine_query_dists(const void* label_u8, const int32_t* q_yx,
 extern "C" int ink_refine_finalize(void* label_u8, const int32_t* assign_yxl, int32_t A, const void* sketch_planes4,
                                    int32_t H, int32_t W, void* planes_ws3, void* extra_plane, int32_t* extra_count,
                                    void* stream) {
-  INK_CHECK_ARG(label_u8 && sketch_planes4 && planes_ws3 && extra_plane && extra_count && H > 0 && W > 0 && A >= 0 &&
-                (A == 0 || assign_yxl));
+  INK_CHECK_ARG(label_u8 && sketch_planes4 && planes_ws3 && extra_plane && extra_count && H > 0 && W > 0 &&
+                H <= 16383 && W <= 16383 && A >= 0 && (A == 0 || assign_yxl));
   hipStream_t s = (hipStream_t)stream;
   const int Wp = (W + 63) / 64;
   const int64_t ps = (int64_t)H * Wp;

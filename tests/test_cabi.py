@@ -84,6 +84,55 @@ def test_attn_fewq_argument_contract():
     assert call(K=None) == 1
 
 
+def test_refine_stage_argument_contract():
+    """The ten entry points of csrc/refine_stage.hip return 1 before any launch for: each required pointer null in
+    turn, H or W of 0, H or W of 16384 where the entry point launches a word grid computed in int or packs run ends into
+    16 bits, 255 ranks, an in-place label image, a cap of 0, P or Q of 0, A < 0.  Fake non-null pointers: none of these
+    calls may be accepted.  (Looked up by name from a table, so these calls do not count as tests of the kernels for
+    tests/test_op_coverage_cpu.py.)"""
+    from inklayer_amd import _lib
+    l = _lib.lib()
+    size0 = [dict(H=0), dict(W=0)]
+    size = size0 + [dict(H=16384), dict(W=16384)]
+    null = lambda *names: [{n: None} for n in names]
+    table = {
+        "ink_refine_sketch_planes": (dict(rgb=16, H=8, W=8, planes=32, max_ws=48),
+                                     null("rgb", "planes", "max_ws") + size),
+        "ink_bitplane_pack": (dict(img=16, n=2, H=8, W=8, thresh=0, planes=32),
+                              null("img", "planes") + size + [dict(n=0), dict(n=-1)]),
+        "ink_refine_depth_samples": (dict(planes=16, n=3, depth=32, pts=48, P=5, H=8, W=8, vals=64, inside=80),
+                                     null("planes", "depth", "pts", "vals", "inside") + size0
+                                     + [dict(P=0), dict(P=-1), dict(n=-1), dict(n=0, depth=None), dict(n=0, vals=None)]),
+        "ink_refine_pair_tables": (dict(planes=16, sk=32, n=2, H=8, W=8, rect=48, dil=64, pair=80, per=96, area=112),
+                                   null("planes", "sk", "rect", "dil", "pair", "per", "area") + size
+                                   + [dict(n=-1), dict(n=0, sk=None), dict(n=0, area=None)]),
+        "ink_refine_composite": (dict(planes=16, order=32, nr=3, H=8, W=8, label=48, hist=64),
+                                 null("planes", "order", "label", "hist") + size
+                                 + [dict(nr=255), dict(nr=-1), dict(nr=0, label=None), dict(nr=0, hist=None)]),
+        "ink_refine_relabel_clean": (dict(label=16, lut=32, H=8, W=8, out=48),
+                                     null("label", "lut", "out") + size0 + [dict(out=16)]),
+        "ink_refine_grow": (dict(label=16, sk=32, H=8, W=8, pws=48, ccw=64, flags=80, out=96, bbox=112, unl=128, cap=4,
+                                 count=144),
+                            null("label", "sk", "pws", "ccw", "flags", "out", "bbox", "unl", "count") + size
+                            + [dict(cap=0), dict(cap=-1), dict(out=16)]),
+        "ink_refine_query_dists": (dict(label=16, q=32, cand=48, Q=3, H=8, W=8, d2=64),
+                                   null("label", "q", "cand", "d2") + size0 + [dict(Q=0), dict(Q=-1)]),
+        "ink_refine_finalize": (dict(label=16, assign=32, A=2, sk=48, H=8, W=8, ws=64, extra=80, count=96),
+                                null("label", "assign", "sk", "ws", "extra", "count") + size
+                                + [dict(A=-1), dict(A=0, label=None), dict(A=0, extra=None)]),
+    }
+    for name, (args, bad) in table.items():
+        fn = getattr(l, name)
+        for kw in bad:
+            assert set(kw) <= set(args), (name, kw)
+            assert fn(*{**args, **kw}.values(), None) == 1, (name, kw)
+    pw, ci = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    ws = getattr(l, "ink_refine_grow_workspace")
+    assert ws(0, 8, ctypes.byref(pw), ctypes.byref(ci)) == 1 and ws(8, 0, ctypes.byref(pw), ctypes.byref(ci)) == 1
+    assert ws(8, 8, None, ctypes.byref(ci)) == 1 and ws(8, 8, ctypes.byref(pw), None) == 1
+    assert ws(7, 129, ctypes.byref(pw), ctypes.byref(ci)) == 0 and pw.value == 4 * 7 * 3 and ci.value > 7 * 7 * 65
+
+
 def test_attn_few_wrappers_refuse_misaligned_rows():
     """ops.attn_fewkeys / ops.attn_fewq assert 16-byte aligned q, k, v before anything native is called (CPU tensors: a
     view that starts 8 bytes into a row)."""

@@ -219,3 +219,83 @@ def test_plugin_surfaces_of_the_stage(dev, tmp_path):
     wfin = R.improve_sam_masks(g["input"], wdis, wboxes)
     assert len(out["final_masks"]) == len(wfin)
     assert all(np.array_equal(np.asarray(a) > 0, np.asarray(b) > 0) for a, b in zip(out["final_masks"], wfin))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# shapes and mask counts the cases above do not reach: more than 1024 rows (a second pass of the row scan), more than
+# 64 words per row, labels past 20, more unlabeled stroke pixels than the growth's first list (the cap retry)
+# ---------------------------------------------------------------------------------------------------------------
+def _rect_masks(rs, h, w, n, min_side, max_h, max_w, fill=0.9):
+    masks, boxes = [], []
+    for i in range(n):
+        x1, y1 = int(rs.randint(0, max(w - min_side, 1))), int(rs.randint(0, max(h - min_side, 1)))
+        x2, y2 = int(min(w, x1 + rs.randint(min_side, max_w))), int(min(h, y1 + rs.randint(min_side, max_h)))
+        m = np.zeros((h, w), bool)
+        m[y1:y2, x1:x2] = rs.rand(y2 - y1, x2 - x1) < fill
+        masks.append(m.astype(np.uint8) * 255)
+        boxes.append([x1, y1, x2, y2])
+    return masks, boxes
+
+
+def test_whole_stage_on_a_sketch_of_1030_rows(dev):
+    from inklayer_amd import synthetic
+    import refine_stage_ref as P
+    h, w = 1030, 70
+    rgb = synthetic.synthetic_sketch(41, h, w)
+    masks, boxes = _rect_masks(np.random.RandomState(1), h, w, 5, 20, 400, 60)
+    boxes[0] = [0, 0, w - 1, h - 1]                               # one box over everything: pixels of every row are assigned
+    res = _assert_stage_equals_oracle(dev, masks, boxes, rgb, _synthetic_depth(h, w, 1), "1030x70")
+    stroke = P.sketch_planes(rgb)[2] & (res.disjoint == 0)       # unlabeled strokes on both sides of row 1024
+    assert stroke[:1024].any() and stroke[1024:].any() and res.n_disjoint >= 2
+
+
+def test_whole_stage_on_a_sketch_of_4100_columns(dev):
+    from inklayer_amd import synthetic
+    import refine_stage_ref as P
+    h, w = 40, 4100
+    rgb = synthetic.synthetic_sketch(42, h, w).copy()
+    masks, boxes = _rect_masks(np.random.RandomState(2), h, w, 6, 15, 40, 1500)
+    masks[0][:, 4090:] = 255                                     # a mask and strokes in the 65th word of the rows
+    boxes[0][2] = w - 1
+    rgb[5:30, 4097:4100] = 0
+    res = _assert_stage_equals_oracle(dev, masks, boxes, rgb, _synthetic_depth(h, w, 2), "40x4100")
+    assert P.sketch_planes(rgb)[2][:, 4096:].any() and res.n_disjoint >= 2
+
+
+def test_whole_stage_with_40_masks(dev):
+    from inklayer_amd import synthetic
+    h, w = 200, 260
+    rs = np.random.RandomState(3)
+    rgb = synthetic.synthetic_sketch(43, h, w)
+    masks, boxes = [], []
+    for gy in range(5):
+        for gx in range(8):
+            x1, y1 = max(0, gx * 32 + int(rs.randint(-6, 4))), max(0, gy * 40 + int(rs.randint(-6, 4)))
+            x2, y2 = min(w, x1 + int(rs.randint(30, 44))), min(h, y1 + int(rs.randint(36, 50)))
+            m = np.zeros((h, w), bool)
+            m[y1:y2, x1:x2] = rs.rand(y2 - y1, x2 - x1) < 0.95
+            masks.append(m.astype(np.uint8) * 255)
+            boxes.append([x1, y1, x2, y2])
+    res = _assert_stage_equals_oracle(dev, masks, boxes, rgb, _synthetic_depth(h, w, 3), "40 masks")
+    assert res.n_disjoint > 20 and res.final.max() > 20
+
+
+def test_whole_stage_on_a_dark_sketch_without_masks(dev):
+    """90000 unlabeled stroke pixels: more than the 65536 pairs of the growth's first list, so the count comes back
+    larger than the cap and the growth runs again; no masks, so no distance queries."""
+    import refine_stage_ref as P
+    rgb = P.dark_sketch(300, 300)
+    res = _assert_stage_equals_oracle(dev, [], [], rgb, _synthetic_depth(300, 300, 4), "dark, no masks")
+    assert res.n_disjoint == 0 and res.extra is not None and int(res.extra.sum()) == 90000
+
+
+def test_whole_stage_on_a_dark_sketch_with_one_mask(dev):
+    """The same sketch with one mask in a larger box: 87000 unlabeled stroke pixels walk through the raster-order
+    assignment (one box: no distance query decides anything), 9000 of them inside the box."""
+    import refine_stage_ref as P
+    rgb = P.dark_sketch(300, 300)
+    one = np.zeros((300, 300), np.uint8)
+    one[100:140, 100:160] = 255
+    res = _assert_stage_equals_oracle(dev, [one], [[80, 80, 200, 180]], rgb, _synthetic_depth(300, 300, 5), "dark, one mask")
+    assert res.n_disjoint == 1 and res.timings["unlabeled pixels"] > 65536
+    assert int((res.final == 1).sum()) == 121 * 101
