@@ -596,7 +596,7 @@ int ink_host_assign_unlabeled(const int32_t* q_yx, int32_t Q, const int32_t* box
                               const int32_t* d2, const uint8_t* nonempty, int32_t n_masks, int32_t* out_label);
 
 /* ------------------------------------------------------------------------
- * Depth-Anything-V2 ViT-B pixel-side ops (the dense layers reuse ink_gemm_f16 / ink_flash_attn /
+ * Depth-Anything-V2 (ViT-S / ViT-B / ViT-L) pixel-side ops (the dense layers reuse ink_gemm_f16 / ink_flash_attn /
  * ink_layernorm_rows).
  *
  * ink_depth_patchify = DepthAnythingV2.image2tensor (DA/dpt.py:199-221: BGR->RGB, /255, cv2.resize INTER_CUBIC to
@@ -618,6 +618,22 @@ int ink_resize_bilinear_ac_nhwc(const float* in, int32_t B, int32_t h, int32_t w
  * DA/dpt.py:72-77): [B*H*W, C] -> [B*OH*OW, 9*C], OH = (H - 1) / stride + 1. */
 int ink_im2col3x3_ex_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t relu,
                          void* out_f16, void* stream);
+
+/* Direct (implicit-GEMM) 3x3 / pad 1 convolution of an NHWC f16 map, stride 1 or 2; the im2col matrix is never
+ * written.  With OH = (H - 1) / stride + 1, OW likewise and M = B*OH*OW:
+ *   out[(b,oy,ox), n] = residual[(b,oy,ox), n]
+ *                       + act( sum_{ky,kx,c} relu_in?( in[b, oy*stride+ky-1, ox*stride+kx-1, c] ) * wt[n, (ky*3+kx)*C + c]
+ *                              + bias[n] )
+ * in f16 [B*H*W, C]; wt f16 [N, 9*C] (a Conv2d weight [N, C, 3, 3] permuted to (n, ky, kx, c)); bias f32 [N] or NULL;
+ * relu_in 0 / 1; act INK_ACT_NONE or INK_ACT_RELU; residual f32 [M, N] or NULL; out f32 (out_f16 = 0) or f16 (1) [M, N].
+ * Replaces the convolutions of the DPT head without their im2col matrices: ResidualConvUnit (DA/util/blocks.py:59-84:
+ * relu_in + bias + ReLU for conv1, bias + residual for conv2), the stride-2 resize conv (DA/dpt.py:72-77), and
+ * layer*_rn / output_conv1 / output_conv2 (DA/dpt.py:92-110).
+ * Returns INK_ERR_ARG with nothing launched unless C % 32 == 0, N % 4 == 0, stride is 1 or 2, every size is positive,
+ * M fits an int32, and in / wt / out / residual / bias are 16-byte aligned.  Added without changing any entry point. */
+int ink_conv3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, const void* wt_f16, int32_t N,
+                    const float* bias, int32_t stride, int32_t relu_in, int32_t act, const float* residual, void* out,
+                    int32_t out_f16, void* stream);
 
 /* ------------------------------------------------------------------------
  * Layer assembly: the reference's inpainting stage around the diffusion model.  Binary images are

@@ -134,6 +134,8 @@ SIGNATURES = {
                            c_int, c_void_p, c_void_p],
     "ink_resize_bilinear_ac_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_im2col3x3_ex_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_conv3x3_f16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                        c_void_p, c_int, c_void_p],
     "ink_layers_otsu_planes": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "ink_layers_dilate": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_layers_border_band": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],

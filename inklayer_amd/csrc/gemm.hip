@@ -15,6 +15,8 @@
 //     M-tiles x all N-tiles at a time, and re-reads its A / W panels from L2;
 //   - epilogue (fused, f32): +bias, GELU/ReLU, *col_scale, +residual (preloaded into the accumulators for linear
 //     GEMMs), optional row scatter (window-unpartition / crop / un-shift), f32 or f16 store as whole row segments.
+// The direct 3x3 convolution of the DPT head (conv3x3_f16_nt, ink_conv3x3_f16) is the generic 128x128 kernel with another
+// A-address generator and shares the accumulator set-up / epilogue; it lives at the end of the namespace.
 // Tile choice: ink_gemm_query_variant (shape heuristic); ink_gemm_set_variant forces one of its tile families (tests).
 #include <stdlib.h>
 
@@ -508,9 +510,201 @@ static int launch_gemm(const InkGemm& p, hipStream_t s, int group_m = 1) {
   return ink_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Direct 3x3 / pad 1 convolution on an NHWC f16 map (ink_conv3x3_f16): gemm_f16_nt<128, 128, BK, 2, 2> with another
+// A-address generator - the im2col matrix [B*OH*OW, 9*C] is never written.  M = B*OH*OW output pixels, K = 9*C in
+// (ky, kx, c) order; BK divides C, so a K-tile lies inside ONE tap and is a contiguous BK-channel run of one input
+// pixel.  A lane's staging chunk belongs to one output pixel for the whole K loop: (b, oy, ox) is decoded once into the
+// pointer of the centre input pixel (with the lane's swizzled chunk folded in, exactly as gemm_f16_nt does) and a
+// 9-bit mask of the taps that fall inside the image; per K-tile the LDS-DMA source is centre + tap offset, or a row of
+// zeros for a padding tap.  RELU_IN applies ResidualConvUnit's activation(x) to the A fragments after the LDS read
+// (packed max with 0; the padding zeros are fixed points).  Accumulators and epilogue are the GEMM's.
+struct ConvGeom {
+  int H, W, C, OH, OW, stride;
+};
+__device__ __attribute__((aligned(128))) const uint32_t g_conv_zero_row[32] = {};   // 64 f16 zeros: one padding tap
+
+template <int BK, bool RELU_IN>
+__global__ __launch_bounds__(256) void conv3x3_f16_nt(InkGemm p, ConvGeom g) {
+  constexpr int BM = 128, BN = 128, WM = 2, WN = 2;
+  constexpr int NT = WM * WN * 64;
+  constexpr int CPR = BK / 8;
+  constexpr int ROWB = BK * 2;
+  constexpr int TILE_A = BM * ROWB, TILE_W = BN * ROWB;
+  constexpr int STAGE = TILE_A + TILE_W;
+  constexpr int IT_A = (BM * CPR) / NT, IT_W = (BN * CPR) / NT;
+  constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+
+  const int ntn = (p.N + BN - 1) / BN;
+  const int ntm = (p.M + BM - 1) / BM;
+  int mt, nt;
+  tile_of(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, 1, mt, nt);
+  const int m0 = mt * BM;
+  const int n0 = nt * BN;
+
+  const f16* __restrict__ A = (const f16*)p.A;
+  const f16* __restrict__ W = (const f16*)p.W;
+
+  const f16* ctrA[IT_A];      // centre input pixel of the chunk's output pixel, + the lane's (swizzled) chunk
+  const f16* zeroA[IT_A];     // the same chunk of the zero row
+  int maskA[IT_A];            // bit ky*3+kx: that tap lies inside the image
+  const f16* srcW[IT_W];
+#pragma unroll
+  for (int it = 0; it < IT_A; ++it) {
+    const int pch = it * NT + tid;
+    const int row = pch / CPR;
+    const int lch = (pch % CPR) ^ Swz<BK>::f(row);
+    const int m = min(m0 + row, p.M - 1);
+    const int b = m / (g.OH * g.OW);
+    const int rem = m - b * (g.OH * g.OW);
+    const int oy = rem / g.OW;
+    const int iy = oy * g.stride, ix = (rem - oy * g.OW) * g.stride;
+    ctrA[it] = A + (((size_t)b * g.H + iy) * g.W + ix) * g.C + lch * 8;
+    zeroA[it] = (const f16*)g_conv_zero_row + lch * 8;
+    const int rowok = (iy > 0 ? 1 : 0) | 2 | (iy + 1 < g.H ? 4 : 0);
+    const int colok = (ix > 0 ? 1 : 0) | 2 | (ix + 1 < g.W ? 4 : 0);
+    int mask = 0;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+      if ((rowok >> ky) & 1) mask |= colok << (ky * 3);
+    maskA[it] = mask;
+  }
+#pragma unroll
+  for (int it = 0; it < IT_W; ++it) {
+    const int pch = it * NT + tid;
+    const int row = pch / CPR;
+    const int lch = (pch % CPR) ^ Swz<BK>::f(row);
+    srcW[it] = W + (size_t)min(n0 + row, p.N - 1) * p.ldw + lch * 8;
+  }
+
+  // K-tiles are staged in order; (tap, c0) of the next one to stage: k = tap * C + c0
+  int s_tap = 0, s_c0 = 0;
+  auto stage = [&](int buf, int kt) {
+    char* base = smem + buf * STAGE;
+    const int ky = s_tap / 3, kx = s_tap - ky * 3;
+    const ptrdiff_t doff = ((ptrdiff_t)(ky - 1) * g.W + (kx - 1)) * g.C + s_c0;
+#pragma unroll
+    for (int it = 0; it < IT_A; ++it) {
+      const f16* src = ((maskA[it] >> s_tap) & 1) ? ctrA[it] + doff : zeroA[it];
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + (it * NT + wave * 64) * 16), 16, 0, 0);
+    }
+#pragma unroll
+    for (int it = 0; it < IT_W; ++it)
+      __builtin_amdgcn_global_load_lds((gptr_t)(srcW[it] + kt * BK), (lptr_t)(base + TILE_A + (it * NT + wave * 64) * 16), 16, 0, 0);
+    s_c0 += BK;
+    if (s_c0 == g.C) {
+      s_c0 = 0;
+      ++s_tap;
+    }
+  };
+
+  int rows[TM];
+  wave_rows<TM>(rows, p, m0 + wm * (BM / WM), lane);
+  f32x4 acc[TM][TN];
+
+  const int fr = lane & 15, fq = lane >> 4;
+  const int offA = (wm * (BM / WM) + fr) * ROWB;
+  const int offW = (wn * (BN / WN) + fr) * ROWB;
+  const int swz = Swz<BK>::f(fr);
+
+  const int nk = p.K / BK;
+  auto compute = [&](int cur) {
+    const char* bA = smem + cur * STAGE;
+    const char* bW = bA + TILE_A;
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+      f16x8 a[TM], w[TN];
+      const int co = ((kk * 4 + fq) ^ swz) << 4;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) w[j] = *(const f16x8*)(bW + offW + j * 16 * ROWB + co);
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        a[i] = *(const f16x8*)(bA + offA + i * 16 * ROWB + co);
+        if (RELU_IN) a[i] = __builtin_elementwise_max(a[i], (f16x8)(f16)0);
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[j], a[i], acc[i][j], 0, 0, 0);
+    }
+  };
+
+  stage(0, 0);
+  init_wave_tile<TM, TN>(acc, p, rows, n0 + wn * (BN / WN), lane);
+  for (int kt = 0; kt < nk; ++kt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA of tile kt (see gemm_f16_nt)
+    __syncthreads();
+    if (kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
+    compute(kt & 1);
+  }
+
+  constexpr int WNC = BN / WN;
+  constexpr int EP = WNC * 4 + 16;
+  static_assert(WM * WN * 16 * EP <= NS * STAGE, "epilogue patch must fit in the staging LDS");
+  __syncthreads();
+  char* er = smem + wave * (16 * EP);
+  if (p.c_f16 == 1) {
+    store_wave_tile<TM, TN, 1>(acc, p, er, rows, n0 + wn * WNC, lane);
+  } else {
+    store_wave_tile<TM, TN, 0>(acc, p, er, rows, n0 + wn * WNC, lane);
+  }
+}
+
+template <int BK, bool RELU_IN>
+static int launch_conv3x3(const InkGemm& p, const ConvGeom& g, hipStream_t s) {
+  constexpr int lds = NS * (128 + 128) * BK * 2;
+  static bool attr = ((void)hipFuncSetAttribute((const void*)conv3x3_f16_nt<BK, RELU_IN>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
+  (void)attr;
+  const int ntm = (p.M + 127) / 128, ntn = (p.N + 127) / 128;
+  hipLaunchKernelGGL((conv3x3_f16_nt<BK, RELU_IN>), dim3(ntm * ntn), dim3(256), lds, s, p, g);
+  return ink_launch_status();
+}
+
 }  // namespace
 
-static int g_variant = -1;   // ink_gemm_set_variant: -1 = the shape heuristic, else the forced tile family
+extern "C" int ink_conv3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, const void* wt_f16,
+                               int32_t N, const float* bias, int32_t stride, int32_t relu_in, int32_t act,
+                               const float* residual, void* out, int32_t out_f16, void* stream) {
+  INK_CHECK_ARG(in_f16 && wt_f16 && out);
+  INK_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
+  INK_CHECK_ARG(C % 32 == 0 && N % 4 == 0);
+  INK_CHECK_ARG(stride == 1 || stride == 2);
+  INK_CHECK_ARG(((uintptr_t)in_f16 & 15) == 0 && ((uintptr_t)wt_f16 & 15) == 0);
+  INK_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)residual & 15) == 0 && ((uintptr_t)bias & 15) == 0);
+  INK_CHECK_ARG(relu_in == 0 || relu_in == 1);
+  INK_CHECK_ARG(act == INK_ACT_NONE || act == INK_ACT_RELU);
+  INK_CHECK_ARG(out_f16 == 0 || out_f16 == 1);
+  const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  const int64_t M = (int64_t)B * OH * OW;
+  INK_CHECK_ARG(M <= INT32_MAX - 128 && (int64_t)9 * C <= INT32_MAX);
+  InkGemm p = {};
+  p.A = in_f16;
+  p.W = wt_f16;
+  p.bias = bias;
+  p.residual = residual;
+  p.C = out;
+  p.M = (int32_t)M;
+  p.N = N;
+  p.K = 9 * C;
+  p.lda = p.ldw = 9 * C;
+  p.ldr = p.ldc = N;
+  p.act = act;
+  p.c_f16 = out_f16;
+  const ConvGeom g = {H, W, C, OH, OW, stride};
+  hipStream_t s = (hipStream_t)stream;
+  if (C % 64 == 0) return relu_in ? launch_conv3x3<64, true>(p, g, s) : launch_conv3x3<64, false>(p, g, s);
+  return relu_in ? launch_conv3x3<32, true>(p, g, s) : launch_conv3x3<32, false>(p, g, s);
+}
+
+static int g_variant = -1;  // ink_gemm_set_variant: -1 = the shape heuristic, else the forced tile family
 // shape heuristic (tile sweeps on MI355X): the ping-pong 256x320 tile when N is a multiple of 320 and
 // the launch is at least ~1.5 rounds of 256 CUs (SAM ViT-H: N = 1280 / 3840 / 5120, where batch 8 gives
 // exact round counts and 10 % fewer staged bytes per flop than 256x256); else the 16-wave 256x256 tile whenever it

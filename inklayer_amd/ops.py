@@ -1104,6 +1104,31 @@ def im2col3x3_ex(x: torch.Tensor, B: int, H: int, W: int, stride: int = 1, relu:
     return out
 
 
+def conv3x3(x16: torch.Tensor, B: int, H: int, W: int, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+            stride: int = 1, relu_in: bool = False, act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = F32) -> torch.Tensor:
+    """Direct 3x3 / pad 1 convolution (ink_conv3x3_f16): out = residual + act(conv(relu_in?(x16), w) + bias).
+
+    x16: f16 NHWC [B*H*W, C]; w: f16 [N, 9*C] in (ky, kx, c) order; bias f32 [N]; residual f32 [B*OH*OW, N];
+    act None / "relu".  -> [B*OH*OW, N] f32 or f16."""
+    assert x16.dtype == F16 and w.dtype == F16 and x16.dim() == 2 and w.dim() == 2
+    assert x16.is_contiguous() and w.is_contiguous() and x16.shape[0] == B * H * W
+    assert stride in (1, 2) and act in (None, "relu")
+    Cn, N = x16.shape[1], w.shape[0]
+    assert w.shape[1] == 9 * Cn
+    M = B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+    if out is None:
+        out = torch.empty((M, N), device=x16.device, dtype=out_dtype)
+    assert out.dtype in (F16, F32) and out.is_contiguous() and tuple(out.shape) == (M, N)
+    if bias is not None:
+        assert bias.dtype == F32 and bias.numel() == N and bias.is_contiguous()
+    if residual is not None:
+        assert residual.dtype == F32 and residual.is_contiguous() and tuple(residual.shape) == (M, N)
+    check(_lib.lib().ink_conv3x3_f16(_p(x16), B, H, W, Cn, _p(w), N, _p(bias), stride, int(relu_in), ACT[act],
+                                     _p(residual), _p(out), int(out.dtype == F16), _stream()), "ink_conv3x3_f16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # Layer assembly (DESIGN §0 row (f)-5): bit planes are int64 [n, H, ceil(W / 64)], images uint8
 # ---------------------------------------------------------------------------------------------

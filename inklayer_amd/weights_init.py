@@ -192,7 +192,7 @@ def random_text_features(cfg, device, n_tokens: int = 4, seed: int = 2) -> torch
 
 
 def depth_param_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
-    """Parameter names/shapes of DepthAnythingV2("vitb") (DA/dpt.py:153-176, DA/dinov2.py:397-415)."""
+    """Parameter names/shapes of DepthAnythingV2(cfg.encoder) (DA/dpt.py:153-176, DA/dinov2.py:339-415)."""
     D, P, Fe = cfg.embed_dim, cfg.patch_size, cfg.features
     g = cfg.img_size // P
     s: Dict[str, Tuple[int, ...]] = {
