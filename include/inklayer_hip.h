@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define INK_ABI_VERSION 8
+#define INK_ABI_VERSION 9
 int ink_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -184,23 +184,27 @@ int ink_sam_patchify(const void* image_u8, int32_t h, int32_t w, int32_t L, int3
                      const float* mean3, const float* std3, int32_t chan_reverse, int32_t split,
                      void* out_f16, void* stream);
 
-/* Pillow's antialiased bilinear resize of an HWC uint8 RGB image, bit for bit: the `F.resize` of
- * load_image (GD/util/inference.py:39-50, GD/datasets/transforms.py:87-117: shorter side 800, max 1333) and
- * ResizeLongestSide.apply_image (SA/utils/transforms.py:26-31, 93-102), both of which end in PIL
- * Image.resize(BILINEAR).  src [h, w, 3] -> dst [oh, ow, 3].  xbounds/ybounds: int32 [ow|oh, 2] = (first
- * input sample, number of samples); xcoef/ycoef: int32 [ow|oh, kx|ky] 22-bit fixed-point weights, both
- * exactly as Pillow's precompute_coeffs + normalize_coeffs_8bpc produce them (inklayer_amd/resize.py).
- * Horizontal pass first, rounded to u8 into tmp [h, ow, 3] (needed only when both sizes change), then
- * the vertical pass.  At least one of the two sizes must differ. */
-int ink_resize_bilinear_u8(const void* src_u8, int32_t h, int32_t w, void* dst_u8, int32_t oh, int32_t ow,
-                           const int32_t* xbounds, const int32_t* xcoef, int32_t kx,
-                           const int32_t* ybounds, const int32_t* ycoef, int32_t ky, void* tmp_u8,
-                           void* stream);
+/* Pillow's 8-bit two-pass resampler (PIL Image.resize with an antialiasing filter) on an HWC uint8 image of 1 or 3
+ * interleaved channels, bit for bit: the bilinear `F.resize` of load_image (GD/util/inference.py:39-50,
+ * GD/datasets/transforms.py:87-117: shorter side 800, max 1333) and of ResizeLongestSide.apply_image
+ * (SA/utils/transforms.py:26-31, 93-102); the inpainting stage's Image.resize(LANCZOS) of images and masks
+ * (inpaint_ControlNet.py:150-151, 161, 176, inpaint_single_layer.py:43-44, 63) and the default bicubic resize of
+ * inpaint_SDXL.py:23-24.  src [h, w, channels] -> dst [oh, ow, channels], not in place, every side <= 16384.
+ * xbounds/ybounds: int32 [ow|oh, 2] = (first input sample, number of samples); xcoef/ycoef: int32 [ow|oh, kx|ky]
+ * 22-bit fixed-point weights, both exactly as Pillow's precompute_coeffs + normalize_coeffs_8bpc produce them for the
+ * filter (inklayer_amd/resize.py::pil_resize_coeffs); the tables of an axis that keeps its size may be NULL.
+ * Horizontal pass first, rounded to u8 into tmp_u8 [h, ow, channels] (needed only when both sizes change), then the
+ * vertical pass.  The same size on both axes is a copy, as Image.resize makes one. */
+int ink_resize_u8(const void* src_u8, int32_t h, int32_t w, int32_t channels, void* dst_u8, int32_t oh, int32_t ow,
+                  const int32_t* xbounds, const int32_t* xcoef, int32_t kx, const int32_t* ybounds,
+                  const int32_t* ycoef, int32_t ky, void* tmp_u8, void* stream);
 
-/* 3x3 / pad-1 im2col of an NHWC f16 map [B,H,W,C] -> [B*H*W, 9*C] with column (ky*3+kx)*C + c
- * (neck conv SA/modeling/image_encoder.py:96-103; GD input_proj 3x3 s2 uses the strided form). */
-int ink_im2col3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, void* out_f16,
-                      void* stream);
+/* 3x3 / pad 1 im2col of an NHWC f16 map with stride 1 or 2 and an optional ReLU applied to the gathered values:
+ * [B*H*W, C] -> [B*OH*OW, 9*C] with column (ky*3+kx)*C + c, OH = (H - 1) / stride + 1, OW likewise; C % 8 == 0.
+ * The neck conv of SA/modeling/image_encoder.py:96-103; ResidualConvUnit's activation(x) before conv1
+ * (DA/util/blocks.py:69-70) and the stride-2 resize conv of DA/dpt.py:72-77. */
+int ink_im2col3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t relu,
+                      void* out_f16, void* stream);
 
 /* PositionEmbeddingRandom._pe_encoding (SA/modeling/prompt_encoder.py:186-193):
  * out[n] = [sin(2*pi*((2c-1) @ G)), cos(2*pi*((2c-1) @ G))], coords01 f32 [N,2] in [0,1]^2,
@@ -613,12 +617,6 @@ int ink_depth_patchify(const void* image_u8, int32_t H, int32_t W, int32_t nh, i
 int ink_resize_bilinear_ac_nhwc(const float* in, int32_t B, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W,
                                 float* out_f32, void* out_f16, void* stream);
 
-/* 3x3 / pad 1 im2col of an NHWC f16 map with stride 1 or 2 and an optional ReLU applied to the gathered values
- * (ResidualConvUnit's activation(x) before conv1, DA/util/blocks.py:69-70; the stride-2 resize conv of
- * DA/dpt.py:72-77): [B*H*W, C] -> [B*OH*OW, 9*C], OH = (H - 1) / stride + 1. */
-int ink_im2col3x3_ex_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t relu,
-                         void* out_f16, void* stream);
-
 /* Direct (implicit-GEMM) 3x3 / pad 1 convolution of an NHWC f16 map, stride 1 or 2; the im2col matrix is never
  * written.  With OH = (H - 1) / stride + 1, OW likewise and M = B*OH*OW:
  *   out[(b,oy,ox), n] = residual[(b,oy,ox), n]
@@ -712,7 +710,8 @@ int ink_layers_rgba(const void* gray_u8, const void* bg_planes, int32_t n, int32
  * Inpainting: pre- and post-processing around the diffusion pipe (csrc/inpaint_ops.hip).  Images are
  * uint8 [H, W, 3] (R, G, B) and uint8 [H, W] on the device.  Every table of exponentials is computed on the host in
  * double precision, rounded once to the stated type and passed in; the kernels do + - x /, compares and conversions in
- * a fixed order and equal tests/inpaint_ref.py bit for bit.  The stencil entry points need H, W >= 3.
+ * a fixed order and equal tests/inpaint_ref.py bit for bit.  The stencil entry points need H, W >= 3.  The stage's
+ * Lanczos and bicubic resizes of images and masks are ink_resize_u8.
  * ------------------------------------------------------------------------ */
 
 /* ImageEnhance.Contrast(image).enhance(factor) (inpaint_ControlNet.py:51-54): mean = round-half-up mean of Pillow's L
@@ -731,14 +730,6 @@ int ink_inp_bilateral(const void* rgb_u8, int32_t H, int32_t W, const float* tab
  * At least one of the two steps must be asked for; not in place. */
 int ink_inp_mask_prepare(const void* mask_u8, int32_t H, int32_t W, int32_t dilate_iterations, int32_t blur,
                          void* tmp2_u8, void* out_u8, void* stream);
-
-/* Pillow's 8-bit two-pass resampler for 1 or 3 interleaved channels and any of its filters: Image.resize(LANCZOS) of
- * inpaint_ControlNet.py:150-151, 161, 176 and inpaint_single_layer.py:43-44, 63, the default bicubic resize of
- * inpaint_SDXL.py:23-24.  Tables as for ink_resize_bilinear_u8, built by inklayer_amd/resize.py::pil_resize_coeffs for
- * the filter; tmp_u8 [h, ow, channels] when both sizes change.  The same size on both axes is a copy. */
-int ink_inp_resize_u8(const void* src_u8, int32_t h, int32_t w, int32_t channels, void* dst_u8, int32_t oh, int32_t ow,
-                      const int32_t* xbounds, const int32_t* xcoef, int32_t kx, const int32_t* ybounds,
-                      const int32_t* ycoef, int32_t ky, void* tmp_u8, void* stream);
 
 /* make_inpaint_condition (inpaint_ControlNet.py:77-90): f32 [3, H, W] planar = v / 255, -1 where mask >= 128. */
 int ink_inp_condition(const void* rgb_u8, const void* mask_u8, int32_t H, int32_t W, float* out_f32, void* stream);

@@ -52,9 +52,9 @@ SIGNATURES = {
     "ink_flash_attn": [C.POINTER(InkAttn), c_void_p],
     "ink_sam_patchify": [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float),
                          c_int, c_int, c_void_p, c_void_p],
-    "ink_im2col3x3_f16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "ink_resize_bilinear_u8": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
-                               c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "ink_im2col3x3_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_resize_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                      c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "ink_sam_pe_encode": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "ink_sam_mask_logits": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_sam_prompt_tokens": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -133,7 +133,6 @@ SIGNATURES = {
     "ink_depth_patchify": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                            c_int, c_void_p, c_void_p],
     "ink_resize_bilinear_ac_nhwc": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "ink_im2col3x3_ex_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "ink_conv3x3_f16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                         c_void_p, c_int, c_void_p],
     "ink_layers_otsu_planes": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -153,8 +152,6 @@ SIGNATURES = {
     "ink_inp_contrast": [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "ink_inp_bilateral": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_inp_mask_prepare": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "ink_inp_resize_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
-                          c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "ink_inp_condition": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_inp_cleanup": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ink_inp_soft_blend": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -289,18 +289,6 @@ __global__ __launch_bounds__(64) void nms_sweep_kernel(const u64* __restrict__ s
 // uint64: the largest area, the earliest first pixel among equals.
 constexpr int RSR_KEY = 0x0fffffff;
 
-__global__ __launch_bounds__(256) void rsr_not_kernel(const u64* __restrict__ in, u64* __restrict__ out, int Hp, int H,
-                                                      int64_t total) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < total) out[i] = ~in[i] & bp_tail_mask((int)(i % Hp), H);
-}
-
-__global__ __launch_bounds__(256) void rsr_or_kernel(const u64* __restrict__ a, const u64* __restrict__ b,
-                                                     u64* __restrict__ out, int64_t total) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < total) out[i] = a[i] | b[i];
-}
-
 // area and first-pixel key per root (atomics over runs; parents are only read)
 __global__ __launch_bounds__(256) void rsr_stats_kernel(int R, int RM, int* __restrict__ ws_all, int64_t ws_stride) {
   const int lane = threadIdx.x & 63;
@@ -444,30 +432,26 @@ extern "C" int ink_mask_small_regions(const void* planes_u64, int32_t k, int32_t
   INK_CHECK_ARG((((uintptr_t)planes_u64 | (uintptr_t)tmp_planes_u64 | (uintptr_t)out_planes_u64 | (uintptr_t)workspace) & 7) == 0);
   hipStream_t s = (hipStream_t)stream;
   const int Hp = (H + 63) / 64, R = W, RM = rsr_rm(H);
-  const int64_t plane = (int64_t)W * Hp, total = plane * k, stride = cc_ws_ints_per_plane(R, RM);
+  const int64_t plane = (int64_t)W * Hp, stride = cc_ws_ints_per_plane(R, RM);
   INK_CHECK_ARG((size_t)4 * Hp * sizeof(u64) <= 64 * 1024);
   int* info = workspace + 4;
   int* ws = workspace + 4 + 4 * (int64_t)k;
   if (hipMemsetAsync(workspace, 0, (size_t)(4 + 4 * (int64_t)k) * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   if (hipMemsetAsync(changed, 0, (size_t)k * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   const u64* src = (const u64*)planes_u64;
-  const dim3 words((unsigned)((total + 255) / 256)), rows((R + 3) / 4, k);
+  const dim3 rows((R + 3) / 4, k);
   if (holes) {
-    hipLaunchKernelGGL(rsr_not_kernel, words, dim3(256), 0, s, src, (u64*)tmp_planes_u64, Hp, H, total);
+    bp_logic(BP_NOT, src, nullptr, nullptr, (u64*)tmp_planes_u64, k, R, H, s);
     src = (const u64*)tmp_planes_u64;
   }
-  hipLaunchKernelGGL(cc_runs_kernel, rows, dim3(256), 0, s, src, plane, R, H, Hp, RM, ws, stride, workspace);
-  hipLaunchKernelGGL(cc_link_kernel, dim3((R + CC_BR - 1) / CC_BR, k), dim3(256), 0, s, R, RM, 1, 0, ws, stride);
-  if (R > CC_BR) hipLaunchKernelGGL(cc_link_kernel, dim3(1, k), dim3(256), 0, s, R, RM, 1, 1, ws, stride);
+  cc_label(src, plane, k, R, H, Hp, RM, 1, ws, workspace, s);
   hipLaunchKernelGGL(rsr_stats_kernel, rows, dim3(256), 0, s, R, RM, ws, stride);
   hipLaunchKernelGGL(rsr_best_kernel, rows, dim3(256), 0, s, R, RM, min_area, ws, stride, info, changed);
   hipLaunchKernelGGL(rsr_decide_kernel, rows, dim3(256), 0, s, R, RM, min_area, holes, ws, stride, (const int*)info);
   // paint the marked runs: the filled holes into tmp (then out = mask | holes), the kept islands straight into out
   u64* painted = holes ? (u64*)tmp_planes_u64 : (u64*)out_planes_u64;
-  hipLaunchKernelGGL(cc_paint_kernel, rows, dim3(256), 4 * Hp * sizeof(u64), s, R, H, Hp, RM, (const int*)ws, stride,
-                     (uint8_t*)nullptr, painted, plane);
+  cc_paint(k, R, H, Hp, RM, ws, nullptr, painted, plane, s);
   if (holes)
-    hipLaunchKernelGGL(rsr_or_kernel, words, dim3(256), 0, s, (const u64*)planes_u64, (const u64*)tmp_planes_u64,
-                       (u64*)out_planes_u64, total);
+    bp_logic(BP_OR, (const u64*)planes_u64, (const u64*)tmp_planes_u64, nullptr, (u64*)out_planes_u64, k, R, H, s);
   return ink_launch_status();
 }

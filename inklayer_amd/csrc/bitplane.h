@@ -8,9 +8,11 @@
 //   * connected components with statistics, RUN based and MULTI-workgroup: runs per row (wave per row, start / end
 //     bits by word logic) -> union of touching runs of adjacent rows inside blocks of CC_BR rows (one workgroup per
 //     block and plane) -> union across the block seams (one workgroup per plane) -> area / bounding box per root by
-//     atomics over runs -> keep / drop per component (stored per run) -> paint.  Every phase is its own launch: no workgroup ever reads
-//     what another workgroup of the SAME launch wrote (per-XCD L2s are not coherent inside a launch).
-// Included by refine.hip (mask cleanup) and refine_stage.hip (disjoint parsing / growth).
+//     atomics over runs -> keep / drop per component (stored per run) -> paint.  Every phase is its own launch (see
+//     cc_label).  The statistics and the keep rule differ per user; labelling and painting are cc_label / cc_paint;
+//   * bp_logic_kernel: NOT / OR of whole planes.
+// Included by refine.hip (mask cleanup), refine_stage.hip (disjoint parsing / growth), layers.hip (layer assembly) and
+// amg.hip (remove_small_regions, on column-major planes: there a "row" is an image column).
 #pragma once
 #include "common.h"
 
@@ -73,6 +75,27 @@ __global__ __launch_bounds__(256) void bp_pack_kernel(const uint8_t* __restrict_
   const bool on = x < W && (int)img[((int64_t)blockIdx.y * H + y) * W + x] > thresh;
   const u64 m = __ballot(on);
   if (lane == 0) planes[(int64_t)blockIdx.y * H * Wp + word] = m;
+}
+
+// Word logic on `np` planes of `rows` rows of W pixels (Wp words each): out = ~a, a | b or a | b | c.  The row tail mask
+// keeps the tail bits 0 under NOT; under OR it is the identity (the invariant above).  One thread per word.
+enum { BP_NOT = 0, BP_OR = 1, BP_OR3 = 2 };
+__global__ __launch_bounds__(256) void bp_logic_kernel(const u64* __restrict__ a, const u64* __restrict__ b,
+                                                       const u64* __restrict__ c, u64* __restrict__ out, int rows,
+                                                       int W, int Wp, int op) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * Wp) return;
+  const int64_t o = (int64_t)blockIdx.y * rows * Wp + idx;
+  u64 r;
+  if (op == BP_NOT) r = ~a[o];
+  else if (op == BP_OR) r = a[o] | b[o];
+  else r = a[o] | b[o] | c[o];
+  out[o] = r & bp_tail_mask(idx % Wp, W);
+}
+static inline void bp_logic(int op, const u64* a, const u64* b, const u64* c, u64* out, int np, int rows, int W,
+                            hipStream_t s) {
+  const int Wp = (W + 63) / 64;
+  hipLaunchKernelGGL(bp_logic_kernel, dim3((rows * Wp + 255) / 256, np), dim3(256), 0, s, a, b, c, out, rows, W, Wp, op);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -308,19 +331,39 @@ __global__ __launch_bounds__(256) void cc_paint_kernel(int H, int W, int Wp, int
     for (int w = lane; w < Wp; w += 64) out_planes[(int64_t)blockIdx.y * out_plane_stride + (int64_t)y * Wp + w] = mine[w];
 }
 
-// host-side launch sequence of the six phases for `np` planes
+// Host side.  A user of the components launches cc_label, then its own statistics and keep / drop kernels (one launch
+// per phase; the verdict goes into bit 31 of the run word), then cc_paint.
+//
+// Phases A and B for `np` planes of H rows: the runs, the unions inside blocks of CC_BR rows, the unions across the
+// block seams.  Every phase is its own launch, and that is a correctness rule: a phase reads what other workgroups
+// wrote in the phase before (run tables, parents), per-XCD L2s are not coherent inside a launch, and only a kernel
+// boundary makes one launch's writes visible to every workgroup of the next.  The same holds for the phases a user adds.
+static inline void cc_label(const u64* planes, int64_t plane_stride, int np, int H, int W, int Wp, int RM, int conn8,
+                            int* ws, int* overflow, hipStream_t s) {
+  const int64_t stride = cc_ws_ints_per_plane(H, RM);
+  hipLaunchKernelGGL(cc_runs_kernel, dim3((H + 3) / 4, np), dim3(256), 0, s, planes, plane_stride, H, W, Wp, RM, ws,
+                     stride, overflow);
+  hipLaunchKernelGGL(cc_link_kernel, dim3((H + CC_BR - 1) / CC_BR, np), dim3(256), 0, s, H, RM, conn8, 0, ws, stride);
+  if (H > CC_BR) hipLaunchKernelGGL(cc_link_kernel, dim3(1, np), dim3(256), 0, s, H, RM, conn8, 1, ws, stride);
+}
+
+// Phase E.  The kernel's LDS (4 rows of Wp words) is needed for plane output only; the caller checks that it fits.
+static inline void cc_paint(int np, int H, int W, int Wp, int RM, const int* ws, uint8_t* out_u8, u64* out_planes,
+                            int64_t out_plane_stride, hipStream_t s) {
+  hipLaunchKernelGGL(cc_paint_kernel, dim3((H + 3) / 4, np), dim3(256), out_u8 ? 0 : 4 * Wp * sizeof(u64), s, H, W, Wp,
+                     RM, ws, cc_ws_ints_per_plane(H, RM), out_u8, out_planes, out_plane_stride);
+}
+
+// the six phases with this file's own statistics (area, bounding box) and keep rule
 static inline int cc_run(const u64* planes, int64_t plane_stride, int np, int H, int W, int Wp, int RM, int conn8,
                          int area_thr, double aspect_thr, int* ws, int* overflow, uint8_t* out_u8, u64* out_planes,
                          int64_t out_plane_stride, hipStream_t s) {
   const int64_t stride = cc_ws_ints_per_plane(H, RM);
   const dim3 rows((H + 3) / 4, np);
-  hipLaunchKernelGGL(cc_runs_kernel, rows, dim3(256), 0, s, planes, plane_stride, H, W, Wp, RM, ws, stride, overflow);
-  hipLaunchKernelGGL(cc_link_kernel, dim3((H + CC_BR - 1) / CC_BR, np), dim3(256), 0, s, H, RM, conn8, 0, ws, stride);
-  if (H > CC_BR) hipLaunchKernelGGL(cc_link_kernel, dim3(1, np), dim3(256), 0, s, H, RM, conn8, 1, ws, stride);
+  cc_label(planes, plane_stride, np, H, W, Wp, RM, conn8, ws, overflow, s);
   hipLaunchKernelGGL(cc_stats_kernel, rows, dim3(256), 0, s, H, RM, ws, stride);
   hipLaunchKernelGGL(cc_decide_kernel, rows, dim3(256), 0, s, H, RM, area_thr, aspect_thr, ws, stride);
-  hipLaunchKernelGGL(cc_paint_kernel, rows, dim3(256), out_u8 ? 0 : 4 * Wp * sizeof(u64), s, H, W, Wp, RM,
-                     (const int*)ws, stride, out_u8, out_planes, out_plane_stride);
+  cc_paint(np, H, W, Wp, RM, ws, out_u8, out_planes, out_plane_stride, s);
   return ink_launch_status();
 }
 

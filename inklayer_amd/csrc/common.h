@@ -54,6 +54,28 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return fmaf(-0.5f * fabsf(x), e, fmaxf(x, 0.0f));
 }
 
+// RGB -> grey of 8-bit pixels: the three fixed-point forms of (0.299, 0.587, 0.114) that the reference's libraries
+// use.  They are DIFFERENT functions - pil_luma differs from the other two in the coefficients' rounding, and the two
+// cv2 forms can differ by one grey level ((0, 3, 217) is 26 in 15 bits and 27 in 14) - and every call site is pinned
+// bit for bit, by its own test, to the one its reference call produces.  Do not swap one for another.
+//   pil_luma    Pillow, Image.convert("L") (Convert.c rgb2l): the sketch's stroke test of the mask cleaner and the
+//               refinement stage (luma < 250 / <= 250), the inpainting stage's contrast mean and grey round trip.
+//   cv_gray15   OpenCV's 15-bit form: what cv2.imread(path, IMREAD_GRAYSCALE) returns for an 8-bit RGB file (libpng's
+//               rgb_to_gray with OpenCV's coefficients) - the refinement stage's fourth sketch plane and the layer
+//               stage's grey sketch - and cv2.cvtColor(COLOR_RGB2GRAY) as the layer stage and the inpainting
+//               stage's adaptive-threshold clean-up are pinned to it (tests/layers_ref.py, tests/inpaint_ref.py).
+//   cv_gray14   OpenCV's 14-bit form: cv2.cvtColor(COLOR_RGB2GRAY) as the visualisation and the evaluation stage are
+//               pinned to it (visualization.py:83; tests/vis_ref.py, tests/evaluate_ref.py, visualize.gray_host).
+__device__ __forceinline__ int pil_luma(unsigned r, unsigned g, unsigned b) {
+  return (int)((19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16);
+}
+__device__ __forceinline__ int cv_gray15(unsigned r, unsigned g, unsigned b) {
+  return (int)((9798u * r + 19235u * g + 3735u * b + 16384u) >> 15);
+}
+__device__ __forceinline__ int cv_gray14(unsigned r, unsigned g, unsigned b) {
+  return (int)((4899u * r + 9617u * g + 1868u * b + 8192u) >> 14);
+}
+
 // bijective XCD-aware block remap: blocks b and b+8 share an XCD (round-robin
 // dispatch); give every XCD a contiguous chunk of logical tiles so neighbouring
 // tiles (sharing an operand panel) hit the same 4 MiB L2.

@@ -1,7 +1,7 @@
 // Pixel-side kernels of the Depth-Anything-V2 path: HBM / latency bound, tiny next to the ViT GEMMs.
 //   reference: DA/dpt.py:189-221 (image2tensor: cv2.INTER_CUBIC resize, normalise), DA/dinov2_layers/patch_embed.py
 //              (14x14 / s14 conv), DA/util/blocks.py + DA/dpt.py:118-150 (bilinear interpolate, align_corners=True;
-//              3x3 convs with ReLU'd inputs, a 3x3 / s2 conv)
+//              3x3 convs with ReLU'd inputs, a 3x3 / s2 conv: their im2col is image_ops.hip's)
 #include "common.h"
 #include "../../include/inklayer_hip.h"
 
@@ -109,31 +109,6 @@ __global__ __launch_bounds__(256) void resize_bilinear_ac_kernel(const float* __
   }
 }
 
-// 3x3 / pad 1 im2col on an NHWC f16 map with a stride and an optional ReLU on the way:
-// out[b, oy, ox][(ky*3+kx)*C + c] = act(in[b, oy*stride + ky - 1, ox*stride + kx - 1][c]).
-__global__ __launch_bounds__(256) void im2col3x3_ex_kernel(const f16* __restrict__ in, int B, int H, int W, int C,
-                                                           int stride, int relu, int OH, int OW, f16* __restrict__ out) {
-  const int cv = C / 8;
-  const int64_t total = (int64_t)B * OH * OW * 9 * cv;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c8 = (int)(i % cv);
-    const int tap = (int)((i / cv) % 9);
-    const int64_t pix = i / (9 * cv);
-    const int x = (int)(pix % OW), y = (int)((pix / OW) % OH);
-    const int64_t b = pix / ((int64_t)OW * OH);
-    const int yy = y * stride + tap / 3 - 1, xx = x * stride + tap % 3 - 1;
-    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-      v = *(const f16x8*)(in + ((b * H + yy) * W + xx) * C + c8 * 8);
-      if (relu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] > (f16)0 ? v[j] : (f16)0;
-      }
-    }
-    *(f16x8*)(out + (pix * 9 + tap) * C + c8 * 8) = v;
-  }
-}
-
 }  // namespace
 
 extern "C" int ink_depth_patchify(const void* image_u8, int32_t H, int32_t W, int32_t nh, int32_t nw, int32_t P,
@@ -157,16 +132,5 @@ extern "C" int ink_resize_bilinear_ac_nhwc(const float* in, int32_t B, int32_t h
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(resize_bilinear_ac_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, B, h, w, C, H, W,
                      out_f32, (f16*)out_f16);
-  return ink_launch_status();
-}
-
-extern "C" int ink_im2col3x3_ex_f16(const void* in_f16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
-                                    int32_t relu, void* out_f16, void* stream) {
-  INK_CHECK_ARG(in_f16 && out_f16 && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && (stride == 1 || stride == 2));
-  const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
-  const int64_t total = (int64_t)B * OH * OW * 9 * (C / 8);
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(im2col3x3_ex_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)in_f16, B, H, W,
-                     C, stride, relu, OH, OW, (f16*)out_f16);
   return ink_launch_status();
 }

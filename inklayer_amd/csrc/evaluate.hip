@@ -25,12 +25,8 @@ namespace {
 #define EVAL_CHUNK 1024              // pixels per workgroup step: 256 lanes x 4
 enum { EVAL_AL_LABELS = 1, EVAL_AL_RANK = 2, EVAL_AL_PRED = 4, EVAL_AL_SKETCH = 8, EVAL_AL_OUT = 16 };
 
-// cv2.cvtColor(COLOR_RGB2GRAY) for uint8, as csrc/visualize.hip and visualize.gray_host
-__device__ __forceinline__ int eval_gray(unsigned r, unsigned g, unsigned b) {
-  return (int)((4899u * r + 9617u * g + 1868u * b + 8192u) >> 14);
-}
-
-// bit j set: pixel p + j exists and is a stroke pixel (grey < 250)
+// bit j set: pixel p + j exists and is a stroke pixel (grey < 250; cv_gray14, as csrc/visualize.hip and
+// visualize.gray_host)
 __device__ __forceinline__ unsigned eval_strokes4(const uint8_t* __restrict__ sk, int channels, int64_t p, int count,
                                                   bool wide) {
   int g[4];
@@ -38,10 +34,10 @@ __device__ __forceinline__ unsigned eval_strokes4(const uint8_t* __restrict__ sk
     if (channels == 3) {
       const uint32_t* w = (const uint32_t*)(sk + 3 * p);
       const uint32_t a = w[0], b = w[1], c = w[2];           // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-      g[0] = eval_gray(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
-      g[1] = eval_gray(a >> 24, b & 255u, (b >> 8) & 255u);
-      g[2] = eval_gray((b >> 16) & 255u, b >> 24, c & 255u);
-      g[3] = eval_gray((c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
+      g[0] = cv_gray14(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
+      g[1] = cv_gray14(a >> 24, b & 255u, (b >> 8) & 255u);
+      g[2] = cv_gray14((b >> 16) & 255u, b >> 24, c & 255u);
+      g[3] = cv_gray14((c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
     } else {
       const uint32_t a = *(const uint32_t*)(sk + p);
       g[0] = a & 255u; g[1] = (a >> 8) & 255u; g[2] = (a >> 16) & 255u; g[3] = a >> 24;
@@ -52,7 +48,7 @@ __device__ __forceinline__ unsigned eval_strokes4(const uint8_t* __restrict__ sk
       g[j] = 255;
       if (j < count) {
         const uint8_t* q = sk + (p + j) * channels;
-        g[j] = channels == 3 ? eval_gray(q[0], q[1], q[2]) : (int)q[0];
+        g[j] = channels == 3 ? cv_gray14(q[0], q[1], q[2]) : (int)q[0];
       }
     }
   }

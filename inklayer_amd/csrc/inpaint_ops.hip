@@ -7,7 +7,7 @@
 //              InkLayer/inpainting/inpaint_ControlNet.py:92-124  (adaptive-threshold clean-up, soft-mask blend)
 //              InkLayer/inpainting/inpaint_ControlNet.py:150-151, 161, 176, 181-182 (Lanczos resizes, grey round trip,
 //              unsharp mask); inpaint_single_layer.py:43-44, 63, 68-78; inpaint_SDXL.py:23-24, 31-32
-// Third-party algorithms restated: Pillow 12.2 (ImageEnhance.Contrast / Image.blend, Resample.c, BoxBlur.c,
+// Third-party algorithms restated: Pillow 12.2 (ImageEnhance.Contrast / Image.blend, BoxBlur.c,
 // UnsharpMask.c, the "L" conversion) and OpenCV (bilateralFilter, dilate, GaussianBlur, adaptiveThreshold, cvtColor).
 // Every kernel does only + - x /, compares and conversions in a fixed order; every table of exponentials comes from the
 // host, rounded once to its type (inklayer_amd/inpaint.py).  The library is built with -ffp-contract=off, so a product
@@ -24,12 +24,6 @@ __device__ __forceinline__ int inp_r101(int i, int n) {      // cv2.BORDER_REFLE
   return i >= n ? 2 * n - 2 - i : i;
 }
 __device__ __forceinline__ int inp_rep(int i, int n) { return min(max(i, 0), n - 1); }   // replicate
-__device__ __forceinline__ int inp_luma(const uint8_t* p) {   // Pillow's RGB -> L
-  return (int)((19595u * p[0] + 38470u * p[1] + 7471u * p[2] + 0x8000u) >> 16);
-}
-__device__ __forceinline__ int inp_cvgray(const uint8_t* p) { // cv2.COLOR_RGB2GRAY (as lay_gray_kernel)
-  return (int)((9798u * p[0] + 19235u * p[1] + 3735u * p[2] + 16384u) >> 15);
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // (a) ImageEnhance.Contrast(img).enhance(f): the mean of the L image as an integer sum (order-free, so deterministic),
@@ -39,7 +33,7 @@ __global__ __launch_bounds__(256) void inp_luma_sum_kernel(const uint8_t* __rest
   __shared__ unsigned part[256];
   unsigned s = 0;                                             // < 2^32: a thread sees at most 2^28 / (256 blocks) pixels
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256)
-    s += (unsigned)inp_luma(rgb + i * 3);
+    s += pil_luma(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
   part[threadIdx.x] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -132,27 +126,7 @@ __global__ __launch_bounds__(256) void inp_blur3_kernel(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// (d) one pass of Pillow's 8-bit resampler (Resample.c ImagingResampleHorizontal_8bpc / Vertical_8bpc) for C interleaved
-// channels: clip8((2^21 + sum in[xmin + x] * k[x]) >> 22); one thread per output sample.  axis 0: along x, 1: along y.
-__global__ __launch_bounds__(256) void inp_resize_pass_kernel(const uint8_t* __restrict__ in, int in_w, int C,
-                                                              uint8_t* __restrict__ out, int out_h, int out_w,
-                                                              const int32_t* __restrict__ bounds,
-                                                              const int32_t* __restrict__ coef, int ksize, int axis) {
-  const int64_t total = (int64_t)out_h * out_w * C;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c = (int)(i % C);
-    const int64_t pix = i / C;
-    const int oy = (int)(pix / out_w), ox = (int)(pix - (int64_t)oy * out_w);
-    const int o = axis == 0 ? ox : oy;
-    const int lo = bounds[2 * o], n = bounds[2 * o + 1];
-    const int32_t* k = coef + (int64_t)o * ksize;
-    const uint8_t* px = axis == 0 ? in + ((int64_t)oy * in_w + lo) * C + c : in + ((int64_t)lo * in_w + ox) * C + c;
-    const int64_t step = axis == 0 ? C : (int64_t)in_w * C;
-    int s = 1 << 21;
-    for (int x = 0; x < n; ++x) s += (int)px[x * step] * k[x];
-    out[i] = (uint8_t)min(max(s >> 22, 0), 255);
-  }
-}
+// (d) the bicubic / Lanczos resizes of images and masks: Pillow's resampler, ink_resize_u8 (image_ops.hip)
 
 // ------------------------------------------------------------------------------------------------------------------
 // (e) make_inpaint_condition: planar f32 [3, H, W] = v / 255, -1 where the mask / 255 > 0.5 (mask >= 128)
@@ -174,9 +148,13 @@ __global__ __launch_bounds__(256) void inp_gauss11_rows_kernel(const uint8_t* __
   if (p >= (int64_t)H * W) return;
   const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
   const uint8_t* row = rgb + (int64_t)y * W * 3;
-  float s = k[0] * (float)inp_cvgray(row + inp_rep(x - 5, W) * 3);
+  auto grey = [&](int xx) {
+    const uint8_t* q = row + inp_rep(xx, W) * 3;
+    return (float)cv_gray15(q[0], q[1], q[2]);
+  };
+  float s = k[0] * grey(x - 5);
   for (int t = 1; t < 11; ++t) {
-    const float a = k[t] * (float)inp_cvgray(row + inp_rep(x + t - 5, W) * 3);
+    const float a = k[t] * grey(x + t - 5);
     s += a;
   }
   rows[p] = s;
@@ -195,7 +173,7 @@ __global__ __launch_bounds__(256) void inp_cleanup_kernel(const uint8_t* __restr
     s += a;
   }
   const int mean = min(max((int)rintf(s), 0), 255);
-  const bool on = inp_cvgray(rgb + p * 3) > mean - 2;
+  const bool on = cv_gray15(rgb[p * 3], rgb[p * 3 + 1], rgb[p * 3 + 2]) > mean - 2;
   thresh[p] = on ? 255 : 0;
   for (int c = 0; c < 3; ++c) clean[p * 3 + c] = on ? 255 : rgb[p * 3 + c];
 }
@@ -238,7 +216,7 @@ __global__ __launch_bounds__(256) void inp_luma_kernel(const uint8_t* __restrict
                                                        uint8_t* __restrict__ out) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npix) return;
-  const uint8_t l = (uint8_t)inp_luma(rgb + p * 3);
+  const uint8_t l = (uint8_t)pil_luma(rgb[p * 3], rgb[p * 3 + 1], rgb[p * 3 + 2]);
   for (int c = 0; c < oc; ++c) out[p * oc + c] = l;
 }
 
@@ -325,35 +303,6 @@ extern "C" int ink_inp_mask_prepare(const void* mask_u8, int32_t H, int32_t W, i
     cur = dst;
   }
   if (blur) hipLaunchKernelGGL(inp_blur3_kernel, grid, dim3(256), 0, s, cur, H, W, (uint8_t*)out_u8);
-  return ink_launch_status();
-}
-
-extern "C" int ink_inp_resize_u8(const void* src_u8, int32_t h, int32_t w, int32_t channels, void* dst_u8, int32_t oh,
-                                 int32_t ow, const int32_t* xbounds, const int32_t* xcoef, int32_t kx,
-                                 const int32_t* ybounds, const int32_t* ycoef, int32_t ky, void* tmp_u8, void* stream) {
-  INK_CHECK_ARG(src_u8 && dst_u8 && src_u8 != dst_u8 && h > 0 && w > 0 && oh > 0 && ow > 0);
-  INK_CHECK_ARG(h <= 16384 && w <= 16384 && oh <= 16384 && ow <= 16384 && (channels == 1 || channels == 3));
-  const bool need_h = ow != w, need_v = oh != h;
-  INK_CHECK_ARG(!need_h || (xbounds && xcoef && kx > 0));
-  INK_CHECK_ARG(!need_v || (ybounds && ycoef && ky > 0));
-  INK_CHECK_ARG(!(need_h && need_v) || tmp_u8);
-  hipStream_t s = (hipStream_t)stream;
-  if (!need_h && !need_v) {                                   // Image.resize to the same size: a copy
-    if (hipMemcpyAsync(dst_u8, src_u8, (size_t)h * w * channels, hipMemcpyDeviceToDevice, s) != hipSuccess)
-      return INK_ERR_LAUNCH;
-    return INK_OK;
-  }
-  auto grid = [](int64_t n) { return (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); };
-  const uint8_t* cur = (const uint8_t*)src_u8;
-  if (need_h) {                       // [h, w] -> [h, ow]
-    uint8_t* o = need_v ? (uint8_t*)tmp_u8 : (uint8_t*)dst_u8;
-    hipLaunchKernelGGL(inp_resize_pass_kernel, dim3(grid((int64_t)h * ow * channels)), dim3(256), 0, s, cur, w, channels, o,
-                       h, ow, xbounds, xcoef, kx, 0);
-    cur = o;
-  }
-  if (need_v)                         // [h, ow] -> [oh, ow]
-    hipLaunchKernelGGL(inp_resize_pass_kernel, dim3(grid((int64_t)oh * ow * channels)), dim3(256), 0, s, cur, ow, channels,
-                       (uint8_t*)dst_u8, oh, ow, ybounds, ycoef, ky, 1);
   return ink_launch_status();
 }
 

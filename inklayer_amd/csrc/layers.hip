@@ -92,21 +92,6 @@ __global__ __launch_bounds__(256) void lay_band_kernel(const u64* __restrict__ p
   if (v) atomicOr(&flags[blockIdx.y], 1);
 }
 
-// op 0: out = ~a; 1: out = a | b; 2: out = a | b | c  (tail bits stay 0)
-__global__ __launch_bounds__(256) void lay_logic_kernel(const u64* __restrict__ a, const u64* __restrict__ b,
-                                                        const u64* __restrict__ c, u64* __restrict__ out, int H, int W,
-                                                        int Wp, int op) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= H * Wp) return;
-  const int64_t o = (int64_t)blockIdx.y * H * Wp + idx;
-  const int w = idx % Wp;
-  u64 r;
-  if (op == 0) r = ~a[o];
-  else if (op == 1) r = a[o] | b[o];
-  else r = a[o] | b[o] | c[o];
-  out[o] = r & bp_tail_mask(w, W);
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Components with the contour statistics of this stage.  Workspace (int32): header LAY_HDR | n blocks of bitplane.h's
 // component workspace | n x [H * RM] Euler sums.  Header: [0] run overflow, [1] number of undecided holes, [2 ..] their
@@ -255,15 +240,12 @@ static int lay_cc(const u64* src, u64* dst, int np, int H, int W, int Wp, int co
   if (hipMemsetAsync(euler, 0, (size_t)np * H * RM * sizeof(int), s) != hipSuccess) return INK_ERR_LAUNCH;
   if (hipMemsetAsync(best, 0, (size_t)np * sizeof(u64), s) != hipSuccess) return INK_ERR_LAUNCH;
   const dim3 rows((H + 3) / 4, np);
-  hipLaunchKernelGGL(cc_runs_kernel, rows, dim3(256), 0, s, src, ps, H, W, Wp, RM, ws, stride, wsbuf);
-  hipLaunchKernelGGL(cc_link_kernel, dim3((H + CC_BR - 1) / CC_BR, np), dim3(256), 0, s, H, RM, conn8, 0, ws, stride);
-  if (H > CC_BR) hipLaunchKernelGGL(cc_link_kernel, dim3(1, np), dim3(256), 0, s, H, RM, conn8, 1, ws, stride);
+  cc_label(src, ps, np, H, W, Wp, RM, conn8, ws, wsbuf, s);
   hipLaunchKernelGGL(lay_stats_kernel, rows, dim3(256), 0, s, src, ps, H, W, Wp, RM, hole, ws, stride, euler);
   if (mode == LAY_LARGEST) hipLaunchKernelGGL(lay_best_kernel, rows, dim3(256), 0, s, H, RM, ws, stride, best);
   hipLaunchKernelGGL(lay_decide_kernel, rows, dim3(256), 0, s, H, W, RM, mode, ws, stride, (const int*)euler,
                      (const u64*)best, wsbuf);
-  hipLaunchKernelGGL(cc_paint_kernel, rows, dim3(256), 4 * Wp * sizeof(u64), s, H, W, Wp, RM, (const int*)ws, stride,
-                     (uint8_t*)nullptr, dst, ps);
+  cc_paint(np, H, W, Wp, RM, ws, nullptr, dst, ps, s);
   return ink_launch_status();
 }
 
@@ -481,11 +463,11 @@ __global__ __launch_bounds__(256) void lay_composite_kernel(const uint8_t* __res
   out[p * 3 + 2] = keep ? b : inpainted[p * 3 + 2];
 }
 
-// cv2.imread(IMREAD_GRAYSCALE) of an 8-bit RGB file: (9798 R + 19235 G + 3735 B + 16384) >> 15
+// cv2.imread(IMREAD_GRAYSCALE) of an 8-bit RGB file: cv_gray15
 __global__ __launch_bounds__(256) void lay_gray_kernel(const uint8_t* __restrict__ rgb, int64_t npix, uint8_t* __restrict__ gray) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npix) return;
-  gray[p] = (uint8_t)((rgb[p * 3] * 9798u + rgb[p * 3 + 1] * 19235u + rgb[p * 3 + 2] * 3735u + 16384u) >> 15);
+  gray[p] = (uint8_t)cv_gray15(rgb[p * 3], rgb[p * 3 + 1], rgb[p * 3 + 2]);
 }
 
 // RGBA layer (fill_object_bg_mask.py:141, 165-177): alpha = grey < 240 or background; colour = grey on sketch pixels,
@@ -572,33 +554,32 @@ extern "C" int ink_layers_components(const void* planes, int32_t n, int32_t H, i
   u64* ta = (u64*)tmp_planes3;
   u64* tb = ta + (int64_t)n * ps;
   u64* tc = tb + (int64_t)n * ps;
-  const dim3 wg(lay_blocks(ps), n);
   if (hipMemsetAsync(workspace, 0, LAY_HDR * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   int rc;
   if (mode == LAY_LARGEST) {
     // the component with the largest outer contour area, then what it surrounds (drawContours of an external contour)
     if ((rc = lay_cc(in, ta, n, H, W, Wp, 1, LAY_LARGEST, 0, workspace, s)) != INK_OK) return rc;
-    hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, (const u64*)ta, (const u64*)nullptr, (const u64*)nullptr, tb, H, W, Wp, 0);
+    bp_logic(BP_NOT, ta, nullptr, nullptr, tb, n, H, W, s);
     if ((rc = lay_cc(tb, tc, n, H, W, Wp, 0, LAY_FILL_ALL, 1, workspace, s)) != INK_OK) return rc;
-    hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, (const u64*)ta, (const u64*)tc, (const u64*)nullptr, out, H, W, Wp, 1);
+    bp_logic(BP_OR, ta, tc, nullptr, out, n, H, W, s);
     return ink_launch_status();
   }
-  hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, in, (const u64*)nullptr, (const u64*)nullptr, ta, H, W, Wp, 0);
+  bp_logic(BP_NOT, in, nullptr, nullptr, ta, n, H, W, s);
   if ((rc = lay_cc(ta, tb, n, H, W, Wp, 0, mode, 1, workspace, s)) != INK_OK) return rc;
   if (mode == LAY_FLOOD) {     // ~flooded | planes = everything but the flooded background component
-    hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, (const u64*)tb, (const u64*)nullptr, (const u64*)nullptr, out, H, W, Wp, 0);
+    bp_logic(BP_NOT, tb, nullptr, nullptr, out, n, H, W, s);
     return ink_launch_status();
   }
   if (mode == LAY_FILL_ALL) {
-    hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, in, (const u64*)tb, (const u64*)nullptr, out, H, W, Wp, 1);
+    bp_logic(BP_OR, in, tb, nullptr, out, n, H, W, s);
     return ink_launch_status();
   }
   // a filled hole is filled as a polygon: with everything it surrounds = the 8-connected components of the
   // complement of the filled holes that do not reach the image edge
-  hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, (const u64*)tb, (const u64*)nullptr, (const u64*)nullptr, ta, H, W, Wp, 0);
+  bp_logic(BP_NOT, tb, nullptr, nullptr, ta, n, H, W, s);
   // (the header keeps the undecided-hole records of the first pass: lay_cc does not clear it)
   if ((rc = lay_cc(ta, tc, n, H, W, Wp, 1, LAY_FILL_ALL, 0, workspace, s)) != INK_OK) return rc;
-  hipLaunchKernelGGL(lay_logic_kernel, wg, dim3(256), 0, s, in, (const u64*)tb, (const u64*)tc, out, H, W, Wp, 2);
+  bp_logic(BP_OR3, in, tb, tc, out, n, H, W, s);
   return ink_launch_status();
 }
 

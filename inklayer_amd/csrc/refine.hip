@@ -94,9 +94,7 @@ __global__ __launch_bounds__(256) void pack_refined_kernel(const uint8_t* __rest
   bool on = false;
   if (p < npix && masks[m * npix + p] != 0) {
     const uint8_t* c = rgb + p * 3;
-    // PIL Image.convert("L"): (R*19595 + G*38470 + B*7471 + 0x8000) >> 16
-    const unsigned l = ((unsigned)c[0] * 19595u + (unsigned)c[1] * 38470u + (unsigned)c[2] * 7471u + 0x8000u) >> 16;
-    on = l < 250u;
+    on = pil_luma(c[0], c[1], c[2]) < 250;
   }
   const unsigned long long b = __ballot(on);
   if ((threadIdx.x & 63) == 0) bits[m * nwords + word] = b;

@@ -45,12 +45,12 @@ __global__ __launch_bounds__(256) void rs_sketch_planes_kernel(const uint8_t* __
   if (x < W) {
     const uint8_t* c = rgb + ((int64_t)y * W + x) * 3;
     const unsigned r = c[0], g = c[1], b = c[2];
-    const unsigned luma = (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16;      // PIL convert("L")
-    const unsigned gray = (r * 9798u + g * 19235u + b * 3735u + 16384u) >> 15;        // libpng rgb_to_gray (cv2.imread)
+    const int luma = pil_luma(r, g, b);          // PIL convert("L")
+    const int gray = cv_gray15(r, g, b);         // libpng rgb_to_gray (cv2.imread)
     b0 = 2 * (int)b <= *maxv;
-    b1 = luma < 250u;
-    b2 = luma <= 250u;
-    b3 = gray < 250u;
+    b1 = luma < 250;
+    b2 = luma <= 250;
+    b3 = gray < 250;
   }
   const u64 m0 = __ballot(b0), m1 = __ballot(b1), m2 = __ballot(b2), m3 = __ballot(b3);
   if (lane == 0) {

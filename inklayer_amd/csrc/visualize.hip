@@ -18,22 +18,18 @@ namespace {
 #define VIS_FAINT 229                // (255 - 229) / 255 > 0.1 >= (255 - 230) / 255  (visualization.py:109)
 enum { VIS_AL_SKETCH = 1, VIS_AL_MASKS = 2, VIS_AL_OUT = 4 };
 
-// cv2.cvtColor(COLOR_RGB2GRAY) for uint8 (visualization.py:83)
-__device__ __forceinline__ int vis_gray(unsigned r, unsigned g, unsigned b) {
-  return (int)((4899u * r + 9617u * g + 1868u * b + 8192u) >> 14);
-}
-
-// grey of the pixels p .. p + 3 (255 for the ones past `count`)
+// grey (cv_gray14: the cv2.cvtColor(COLOR_RGB2GRAY) of visualization.py:83) of the pixels p .. p + 3 (255 for the ones
+// past `count`)
 __device__ __forceinline__ void vis_gray4(const uint8_t* __restrict__ sk, int channels, int64_t p, int count, bool wide,
                                           int g[4]) {
   if (wide && count == 4) {
     if (channels == 3) {
       const uint32_t* w = (const uint32_t*)(sk + 3 * p);
       const uint32_t a = w[0], b = w[1], c = w[2];           // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-      g[0] = vis_gray(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
-      g[1] = vis_gray(a >> 24, b & 255u, (b >> 8) & 255u);
-      g[2] = vis_gray((b >> 16) & 255u, b >> 24, c & 255u);
-      g[3] = vis_gray((c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
+      g[0] = cv_gray14(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
+      g[1] = cv_gray14(a >> 24, b & 255u, (b >> 8) & 255u);
+      g[2] = cv_gray14((b >> 16) & 255u, b >> 24, c & 255u);
+      g[3] = cv_gray14((c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
     } else {
       const uint32_t a = *(const uint32_t*)(sk + p);
       g[0] = a & 255u; g[1] = (a >> 8) & 255u; g[2] = (a >> 16) & 255u; g[3] = a >> 24;
@@ -45,7 +41,7 @@ __device__ __forceinline__ void vis_gray4(const uint8_t* __restrict__ sk, int ch
     g[j] = 255;
     if (j < count) {
       const uint8_t* q = sk + (p + j) * channels;
-      g[j] = channels == 3 ? vis_gray(q[0], q[1], q[2]) : (int)q[0];
+      g[j] = channels == 3 ? cv_gray14(q[0], q[1], q[2]) : (int)q[0];
     }
   }
 }

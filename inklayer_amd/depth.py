@@ -283,7 +283,7 @@ class DepthEngine:
         C = x16.shape[1]
         M = B * ((hh - 1) // stride + 1) * ((ww - 1) // stride + 1)
         if M <= CONV_ON_PAIR.get((C, wt.shape[0], stride, bool(relu_in)), 0):
-            col = ops.im2col3x3_ex(x16, B, hh, ww, stride=stride, relu=relu_in)
+            col = ops.im2col3x3(x16, B, hh, ww, stride=stride, relu=relu_in)
             return ops.gemm(col, wt, self.w[bias] if bias else None, **kw)
         return ops.conv3x3(x16, B, hh, ww, wt, self.w[bias] if bias else None, stride=stride, relu_in=relu_in, **kw)
 
@@ -393,7 +393,7 @@ class DepthEngine:
         return out
 
 
-# The head's 3x3 convolutions that stay on ops.im2col3x3_ex + ops.gemm: (C, N, stride, relu_in) -> the largest row count
+# The head's 3x3 convolutions that stay on ops.im2col3x3 + ops.gemm: (C, N, stride, relu_in) -> the largest row count
 # M = B*OH*OW at which tools/depth_time.py measured the direct kernel slower than the pair beyond the run-to-run spread
 # (profiles/depth_conv_times.txt, 518 x 518 input, by 2 .. 8 %).  All are launches of three M-tiles with a long K loop
 # on the 19 x 19 map (361 rows): resize_layers.3 and layer4_rn of the three models and ViT-L's ResidualConvUnit conv1

@@ -331,23 +331,31 @@ def relpos_bias(q: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tenso
     return aug
 
 
-def resize_bilinear_u8(image_u8: torch.Tensor, oh: int, ow: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """PIL `Image.resize((ow, oh), BILINEAR)` of an HWC uint8 RGB CUDA tensor, bit for bit (antialiased)."""
+def _resize_u8(image_u8: torch.Tensor, oh: int, ow: int, filter: str, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """Pillow's resampler on a contiguous uint8 [H, W] or [H, W, 3] CUDA tensor: the plan of tables for the sizes and
+    the filter, then the one C call."""
     from .resize import plan_for
-    assert image_u8.dtype == torch.uint8 and image_u8.is_cuda and image_u8.is_contiguous()
-    h, w, c = image_u8.shape
-    assert c == 3
-    if (oh, ow) == (h, w):
-        return image_u8
-    pl = plan_for(h, w, oh, ow, image_u8.device)
+    assert image_u8.dtype == torch.uint8 and image_u8.is_cuda and image_u8.is_contiguous() and oh > 0 and ow > 0
+    assert image_u8.dim() == 2 or (image_u8.dim() == 3 and image_u8.shape[2] == 3), "[H, W] or [H, W, 3] expected"
+    h, w, ch = int(image_u8.shape[0]), int(image_u8.shape[1]), 1 if image_u8.dim() == 2 else 3
+    shape = (oh, ow) if ch == 1 else (oh, ow, 3)
     if out is None:
-        out = torch.empty((oh, ow, 3), device=image_u8.device, dtype=torch.uint8)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (oh, ow, 3)
+        out = torch.empty(shape, device=image_u8.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape
+    pl = plan_for(h, w, oh, ow, image_u8.device, filter, ch)
     ptr = lambda t: t.data_ptr() if t is not None else None
-    check(_lib.lib().ink_resize_bilinear_u8(image_u8.data_ptr(), h, w, out.data_ptr(), oh, ow, ptr(pl.xb), ptr(pl.xk),
-                                            pl.kx, ptr(pl.yb), ptr(pl.yk), pl.ky, ptr(pl.tmp), _stream()),
-          "ink_resize_bilinear_u8")
+    check(_lib.lib().ink_resize_u8(image_u8.data_ptr(), h, w, ch, out.data_ptr(), oh, ow, ptr(pl.xb), ptr(pl.xk), pl.kx,
+                                   ptr(pl.yb), ptr(pl.yk), pl.ky, ptr(pl.tmp), _stream()), "ink_resize_u8")
     return out
+
+
+def resize_bilinear_u8(image_u8: torch.Tensor, oh: int, ow: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PIL `Image.resize((ow, oh), BILINEAR)` of an HWC uint8 RGB CUDA tensor, bit for bit (antialiased).  The same
+    size returns the input itself."""
+    assert image_u8.dim() == 3 and image_u8.shape[2] == 3
+    if (oh, ow) == tuple(image_u8.shape[:2]):
+        return image_u8
+    return _resize_u8(image_u8, oh, ow, "bilinear", out)
 
 
 def sam_patchify(image_u8: torch.Tensor, L: int, P: int, mean: Sequence[float],
@@ -364,13 +372,16 @@ def sam_patchify(image_u8: torch.Tensor, L: int, P: int, mean: Sequence[float],
     return out
 
 
-def im2col3x3(x: torch.Tensor, B: int, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """f16 NHWC [B*H*W, C] -> [B*H*W, 9*C] (pad 1)."""
+def im2col3x3(x: torch.Tensor, B: int, H: int, W: int, stride: int = 1, relu: bool = False,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f16 NHWC [B*H*W, C] -> [B*OH*OW, 9*C] (pad 1, stride 1 or 2, optional ReLU on the gathered values)."""
     assert x.dtype == F16 and x.is_contiguous() and x.shape[0] == B * H * W
     Cn = x.shape[1]
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
     if out is None:
-        out = torch.empty((B * H * W, 9 * Cn), device=x.device, dtype=F16)
-    check(_lib.lib().ink_im2col3x3_f16(x.data_ptr(), B, H, W, Cn, out.data_ptr(), _stream()),
+        out = torch.empty((B * OH * OW, 9 * Cn), device=x.device, dtype=F16)
+    assert out.dtype == F16 and out.is_contiguous() and out.numel() >= B * OH * OW * 9 * Cn
+    check(_lib.lib().ink_im2col3x3_f16(x.data_ptr(), B, H, W, Cn, stride, int(relu), out.data_ptr(), _stream()),
           "ink_im2col3x3_f16")
     return out
 
@@ -1093,17 +1104,6 @@ def resize_bilinear_ac(x: torch.Tensor, B: int, h: int, w: int, H: int, W: int, 
     return out
 
 
-def im2col3x3_ex(x: torch.Tensor, B: int, H: int, W: int, stride: int = 1, relu: bool = False) -> torch.Tensor:
-    """f16 NHWC [B*H*W, C] -> [B*OH*OW, 9*C] (pad 1, stride 1 or 2, optional ReLU on the gathered values)."""
-    assert x.dtype == F16 and x.is_contiguous() and x.shape[0] == B * H * W
-    Cn = x.shape[1]
-    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    out = torch.empty((B * OH * OW, 9 * Cn), device=x.device, dtype=F16)
-    check(_lib.lib().ink_im2col3x3_ex_f16(x.data_ptr(), B, H, W, Cn, stride, int(relu), out.data_ptr(), _stream()),
-          "ink_im2col3x3_ex_f16")
-    return out
-
-
 def conv3x3(x16: torch.Tensor, B: int, H: int, W: int, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
             stride: int = 1, relu_in: bool = False, act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = F32) -> torch.Tensor:
@@ -1442,17 +1442,7 @@ def inp_mask_prepare(mask_u8: torch.Tensor, dilate_iterations: int = 1, blur: bo
 def inp_resize_u8(image_u8: torch.Tensor, oh: int, ow: int, filter: str = "lanczos") -> torch.Tensor:
     """PIL `Image.resize((ow, oh), filter)` of a uint8 [H, W] or [H, W, 3] CUDA tensor, bit for bit; filter is
     "bilinear", "bicubic" or "lanczos".  The same size gives a copy."""
-    from .resize import plan_for
-    assert image_u8.dim() in (2, 3)
-    ch = 1 if image_u8.dim() == 2 else 3
-    h, w = _check_img(image_u8, ch, "inp_resize_u8")
-    assert oh > 0 and ow > 0
-    pl = plan_for(h, w, oh, ow, image_u8.device, filter, ch)
-    out = torch.empty((oh, ow) if ch == 1 else (oh, ow, 3), device=image_u8.device, dtype=torch.uint8)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    check(_lib.lib().ink_inp_resize_u8(image_u8.data_ptr(), h, w, ch, out.data_ptr(), oh, ow, ptr(pl.xb), ptr(pl.xk), pl.kx,
-                                       ptr(pl.yb), ptr(pl.yk), pl.ky, ptr(pl.tmp), _stream()), "ink_inp_resize_u8")
-    return out
+    return _resize_u8(image_u8, oh, ow, filter, None)
 
 
 def inp_condition(rgb_u8: torch.Tensor, mask_u8: torch.Tensor) -> torch.Tensor:

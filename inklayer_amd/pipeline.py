@@ -178,7 +178,7 @@ class InkLayerPipeline:
                 for d, (off, n, h, w) in zip(t.dets, t.views)]
 
     def preprocess(self, raw: Sequence[torch.Tensor]):
-        """GPU side of load_image / ResizeLongestSide (Pillow-exact bilinear, `ink_resize_bilinear_u8`).  SAM's
+        """GPU side of load_image / ResizeLongestSide (Pillow-exact bilinear, `ink_resize_u8`).  SAM's
         channel quirk (InkLayer/segmentor/sam.py:24-26 feeds the encoder channel-reversed pixels) is applied by the
         patchify kernel (chan_reverse), not by a copy."""
         det_in, sam_in, sizes = [], [], []

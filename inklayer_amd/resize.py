@@ -4,7 +4,10 @@ The reference resizes with PIL (torchvision `F.resize` on a PIL image -> `Image.
 detector (GD/datasets/transforms.py:87-117) and once for SAM (SA/utils/transforms.py:26-31).  Pillow's 8-bit
 resampler is integer arithmetic on 22-bit fixed-point weights; the weights and sample bounds are computed here
 exactly as `precompute_coeffs` / `normalize_coeffs_8bpc` (Pillow 12.2 src/libImaging/Resample.c) do, in the same
-double-precision operation order, and the two passes run in `ink_resize_bilinear_u8`.  The inpainting stage resizes\nwith the bicubic and Lanczos filters and single-channel masks as well (inpaint_ControlNet.py:150-151, 176,\ninpaint_SDXL.py:23-24, 31): `pil_resize_coeffs` builds the tables for all three filters, `ink_inp_resize_u8` runs them.
+double-precision operation order, and the two passes run in `ink_resize_u8`.  The inpainting stage resizes with the
+bicubic and Lanczos filters and single-channel masks as well (inpaint_ControlNet.py:150-151, 176,
+inpaint_SDXL.py:23-24, 31): `pil_resize_coeffs` builds the tables for all three filters, and the same entry point
+runs them.
 """
 from __future__ import annotations
 

@@ -36,16 +36,32 @@ def test_pixel_ops_match_torch(dev):
     ref = torch.nn.functional.interpolate(one.view(1, 1, 30, 40), (75, 100), mode="bilinear", align_corners=True).reshape(-1, 1)
     assert (ops.resize_bilinear_ac(one.to(dev), 1, 30, 40, 75, 100).cpu() - ref).abs().max().item() < 2e-6
     # im2col: stride 1 / 2, ReLU on the way
-    m = torch.randn(2 * 9 * 11, 16, generator=g).half()
-    for stride, relu in ((1, False), (1, True), (2, False)):
-        src = m.float().view(2, 9, 11, 16).permute(0, 3, 1, 2)
+    def unfold_ref(m, B, H, W, stride, relu):
+        C = m.shape[1]
+        src = m.float().view(B, H, W, C).permute(0, 3, 1, 2)
         if relu:
             src = src.relu()
         u = torch.nn.functional.unfold(src, 3, padding=1, stride=stride)            # [B, C*9, L] with (c, ky, kx) order
         L = u.shape[-1]
-        ref = u.view(2, 16, 9, L).permute(0, 3, 2, 1).reshape(2 * L, 9 * 16)         # -> [(b, pix), (tap, c)]
-        got = ops.im2col3x3_ex(m.to(dev), 2, 9, 11, stride=stride, relu=relu)
-        assert torch.equal(got.cpu().float(), ref)
+        return u.view(B, C, 9, L).permute(0, 3, 2, 1).reshape(B * L, 9 * C)          # -> [(b, pix), (tap, c)]
+
+    m = torch.randn(2 * 9 * 11, 16, generator=g).half()
+    for stride, relu in ((1, False), (1, True), (2, False)):
+        got = ops.im2col3x3(m.to(dev), 2, 9, 11, stride=stride, relu=relu)
+        assert torch.equal(got.cpu().float(), unfold_ref(m, 2, 9, 11, stride, relu))
+    # odd sizes, two images (the batch offset), 5 x 7 -> 5 x 7 and 3 x 4; the result allocated or written into `out`
+    for C in (8, 24):
+        m = torch.randn(2 * 5 * 7, C, generator=g).half()
+        assert (m < 0).any()
+        for stride in (1, 2):
+            for relu in (False, True):
+                ref = unfold_ref(m, 2, 5, 7, stride, relu)
+                assert ref.shape[0] == 2 * (35 if stride == 1 else 12)
+                got = ops.im2col3x3(m.to(dev), 2, 5, 7, stride=stride, relu=relu)
+                assert tuple(got.shape) == tuple(ref.shape) and torch.equal(got.cpu().float(), ref)
+                out = torch.full(ref.shape, float("nan"), dtype=torch.float16, device=dev)
+                assert ops.im2col3x3(m.to(dev), 2, 5, 7, stride=stride, relu=relu, out=out) is out
+                assert torch.equal(out.cpu().float(), ref)
 
 
 @torch.no_grad()

@@ -149,7 +149,7 @@ def test_layernorm_rows_768(dev):
 @torch.no_grad()
 @pytest.mark.parametrize("H,W,C,stride,relu", [(518, 686, 64, 1, False), (37, 49, 768, 2, False), (148, 148, 128, 1, True)])
 def test_im2col3x3_production_sizes(dev, H, W, C, stride, relu):
-    """im2col3x3_ex on the output_conv2 input (518 x 686 x 64: 204 M output elements, 64-bit flat indices), the stride-2
+    """im2col3x3 on the output_conv2 input (518 x 686 x 64: 204 M output elements, 64-bit flat indices), the stride-2
     resize_layers.3 input at odd sizes, and an RCU input with the ReLU on the way; the input holds -0.0, zeros and
     negative values.  Bit-exact (sign of zero included) against F.unfold; the ReLU maps -0.0 and negatives to +0."""
     from inklayer_amd import ops
@@ -157,7 +157,7 @@ def test_im2col3x3_production_sizes(dev, H, W, C, stride, relu):
     x.view(-1)[5::97] = -0.0
     x.view(-1)[11::89] = 0.0
     assert (x < 0).any() and (x.view(torch.int16) == -32768).any()
-    got = ops.im2col3x3_ex(x, 1, H, W, stride=stride, relu=relu)
+    got = ops.im2col3x3(x, 1, H, W, stride=stride, relu=relu)
     src = x.float().view(1, H, W, C).permute(0, 3, 1, 2)
     if relu:
         src = torch.where(src > 0, src, torch.zeros((), device=dev))
@@ -167,7 +167,7 @@ def test_im2col3x3_production_sizes(dev, H, W, C, stride, relu):
     ref = u.view(C, 9, L).permute(2, 1, 0).reshape(L, 9 * C).half()
     del u, src
     assert torch.equal(got.view(torch.int16), ref.view(torch.int16))
-    print(f"  im2col3x3_ex {H}x{W}x{C} stride {stride} relu {relu}: {got.numel()} elements bit-exact")
+    print(f"  im2col3x3 {H}x{W}x{C} stride {stride} relu {relu}: {got.numel()} elements bit-exact")
 
 
 @torch.no_grad()

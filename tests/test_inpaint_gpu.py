@@ -129,6 +129,39 @@ def test_resampler_equals_pillow(dev, shape, filt):
         assert ops.inp_resize_u8(src, H, W, filt).data_ptr() != src.data_ptr()      # the same size: a copy
 
 
+@pytest.mark.parametrize("filt", sorted(FILTERS))
+def test_resampler_small_edges(dev, filt):
+    """The one resampler behind both wrappers at 37 x 53, one channel and three: one axis shrinks while the other grows
+    (two kernel widths, the intermediate image in use), one axis only (no intermediate, no table for the other axis),
+    down to a single pixel, and the same size through both wrappers."""
+    from PIL import Image
+    from inklayer_amd import ops
+    from inklayer_amd.resize import plan_for
+    H, W = 37, 53
+    rng = np.random.default_rng(37 * 53)
+    rgb = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+    rgb[:9] = 255                                                       # saturated areas: the clipping of overshoots
+    rgb[9:14, ::5] = 0
+    pil_filter = getattr(Image, FILTERS[filt])
+    for a in (rgb, np.ascontiguousarray(rgb[..., 1])):
+        src, ch = _dev(a, dev), (3 if a.ndim == 3 else 1)
+        for oh, ow in ((19, 71), (H, 20), (64, W), (1, 1)):
+            pl = plan_for(H, W, oh, ow, dev, filt, ch)
+            assert (pl.tmp is None) == (oh == H or ow == W) and (pl.xb is None) == (ow == W) and (pl.yb is None) == (oh == H)
+            if (oh, ow) == (19, 71):
+                assert pl.kx != pl.ky
+            want = np.asarray(Image.fromarray(a).resize((ow, oh), pil_filter))
+            assert _eq(ops.inp_resize_u8(src, oh, ow, filt), want), (filt, ch, oh, ow)
+            if ch == 3 and filt == "bilinear":
+                assert _eq(ops.resize_bilinear_u8(src, oh, ow), want), (ch, oh, ow)
+                out = torch.zeros((oh, ow, 3), dtype=torch.uint8, device=dev)
+                assert ops.resize_bilinear_u8(src, oh, ow, out=out) is out and _eq(out, want)
+        same = ops.inp_resize_u8(src, H, W, filt)                       # the same size: a copy ...
+        assert same.data_ptr() != src.data_ptr() and _eq(same, a)
+        if ch == 3:
+            assert ops.resize_bilinear_u8(src, H, W) is src             # ... or the input itself
+
+
 @pytest.mark.parametrize("shape", SHAPES)
 def test_lanczos_round_trip_and_condition(dev, shape):
     from PIL import Image

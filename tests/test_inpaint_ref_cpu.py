@@ -160,9 +160,9 @@ def test_inpaint_entry_points_reject_bad_arguments_without_launch():
     assert l.ink_inp_mask_prepare(p, 8, 8, 0, 0, q, r, None) == 1                # nothing to do
     assert l.ink_inp_mask_prepare(p, 8, 8, 1, 2, q, r, None) == 1
     assert l.ink_inp_mask_prepare(p, 8, 8, -1, 1, q, r, None) == 1
-    assert l.ink_inp_resize_u8(p, 8, 8, 2, q, 4, 4, r, r, 3, r, r, 3, r, None) == 1      # 1 or 3 channels
-    assert l.ink_inp_resize_u8(p, 8, 8, 3, q, 4, 4, None, r, 3, r, r, 3, r, None) == 1
-    assert l.ink_inp_resize_u8(p, 8, 8, 3, q, 4, 4, r, r, 3, r, r, 3, None, None) == 1   # both passes need tmp
+    assert l.ink_resize_u8(p, 8, 8, 2, q, 4, 4, r, r, 3, r, r, 3, r, None) == 1          # 1 or 3 channels
+    assert l.ink_resize_u8(p, 8, 8, 3, q, 4, 4, None, r, 3, r, r, 3, r, None) == 1
+    assert l.ink_resize_u8(p, 8, 8, 3, q, 4, 4, r, r, 3, r, r, 3, None, None) == 1       # both passes need tmp
     assert l.ink_inp_condition(p, None, 8, 8, q, None) == 1
     assert l.ink_inp_cleanup(p, 8, 8, None, q, r, 1024, None) == 1
     assert l.ink_inp_cleanup(p, 8, 8, q, r, 1024, p, None) == 1                  # in place
@@ -171,7 +171,7 @@ def test_inpaint_entry_points_reject_bad_arguments_without_launch():
     assert l.ink_inp_unsharp(p, 8, 8, 3, 15379114, 1, 150, 3, q, r, None) == 1   # fw is not (2^24 - ww) / 2
     assert l.ink_inp_unsharp(p, 8, 8, 2, 15379114, 699051, 150, 3, q, r, None) == 1
     assert l.ink_inp_rgba_cut(p, p, 0, 8, q, None) == 1
-    assert l.ink_abi_version() == 8
+    assert l.ink_abi_version() == 9
 
 
 def test_small_images_raise_value_error():

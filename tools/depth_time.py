@@ -1,7 +1,7 @@
 """Times the DPT head's 3x3 convolutions and batched depth inference on the GPU (it fails without one).
 
   convolutions   every 3x3 convolution shape of the ViT-S / ViT-B / ViT-L heads at a 518 x 518 input (37 x 37 patches),
-                 with the epilogue the engine uses: ops.conv3x3 (the direct kernel) against ops.im2col3x3_ex + ops.gemm
+                 with the epilogue the engine uses: ops.conv3x3 (the direct kernel) against ops.im2col3x3 + ops.gemm
                  (the pair it replaces) on the same seeded operands.  The two are ALTERNATED call by call in one process
                  after --warmup calls of each, every call between two HIP events; one pass gives the median of --iters
                  calls of each, and the whole alternation is repeated --reps times: the report shows the lowest and the
@@ -88,7 +88,7 @@ def measure_convs(a, dev):
                 ops.conv3x3(x, 1, H, W, w, b, stride=stride, relu_in=relu_in, act=act, residual=r, out=out_a)
 
             def pair():
-                ops.gemm(ops.im2col3x3_ex(x, 1, H, W, stride=stride, relu=relu_in), w, b, act=act, residual=r, out=out_b)
+                ops.gemm(ops.im2col3x3(x, 1, H, W, stride=stride, relu=relu_in), w, b, act=act, residual=r, out=out_b)
 
             direct()
             pair()
@@ -177,7 +177,7 @@ def main():
         sys.exit("tools/depth_time.py measures on the GPU: no device found")
     dev = torch.device("cuda:0")
     lines = [f"DPT head 3x3 convolutions and batched depth inference on one {torch.cuda.get_device_name(0)}",
-             f"convolutions: B = 1; direct = ops.conv3x3, pair = ops.im2col3x3_ex + ops.gemm, alternated call by call; each "
+             f"convolutions: B = 1; direct = ops.conv3x3, pair = ops.im2col3x3 + ops.gemm, alternated call by call; each "
              f"figure is the median of {a.iters} calls between two HIP events (wrapper and the pair's matrix allocation "
              f"included), lowest..highest over {a.reps} passes; ratio = direct / pair (medians of the pass medians); MB = "
              "bytes the form has to move, from the shapes", ""]
