@@ -360,9 +360,9 @@ extern "C" int ink_sam_amg_stats(const float* low, int32_t n, const int32_t* ind
   INK_CHECK_ARG(low && table && planes_u64 && n > 0 && m > 0 && (index || m <= n) && S > 0 && L >= S);
   INK_CHECK_ARG(in_h > 0 && in_w > 0 && in_h <= L && in_w <= L && crop_h > 0 && crop_w > 0);
   INK_CHECK_ARG(x0 >= 0 && y0 >= 0 && orig_h <= 16383 && orig_w <= 16383 && x0 + crop_w <= orig_w && y0 + crop_h <= orig_h);
-  INK_CHECK_ARG((int64_t)m * crop_h < (int64_t)1 << 30 && ((uintptr_t)planes_u64 & 7) == 0 && m <= 65535);
+  INK_CHECK_ARG((int64_t)m * crop_h < (int64_t)1 << 30 && ink_aligned<8>(planes_u64) && m <= 65535);
   const bool rows = crop_w % POST_PX == 0;               // ink_sam_postprocess's choice for the same crop size
-  INK_CHECK_ARG(!rows || ((uintptr_t)out_logits & 15) == 0);
+  INK_CHECK_ARG(!rows || ink_aligned<16>(out_logits));
   hipStream_t s = (hipStream_t)stream;
   const int Hp = (orig_h + 63) / 64, band0 = y0 / 64, nb = (y0 + crop_h - 1) / 64 - band0 + 1;
   if (hipMemsetAsync(table, 0, (size_t)m * AMG_T * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
@@ -382,7 +382,7 @@ extern "C" int ink_sam_amg_stats(const float* low, int32_t n, const int32_t* ind
 }
 
 static int rle_check(const void* planes, int32_t k, int32_t H, int32_t W) {
-  INK_CHECK_ARG(planes && ((uintptr_t)planes & 7) == 0 && k > 0 && H > 0 && W > 0 && H <= 16383 && W <= 16383);
+  INK_CHECK_ARG(planes && ink_aligned<8>(planes) && k > 0 && H > 0 && W > 0 && H <= 16383 && W <= 16383);
   return INK_OK;
 }
 
@@ -407,7 +407,7 @@ extern "C" int ink_box_nms(const float* boxes, const float* scores, int32_t n, f
   INK_CHECK_ARG(n_keep && n >= 0 && n <= NMS_MAX);
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return hipMemsetAsync(n_keep, 0, sizeof(int32_t), s) == hipSuccess ? INK_OK : INK_ERR_LAUNCH;
-  INK_CHECK_ARG(boxes && scores && keep && workspace_u64 && ((uintptr_t)workspace_u64 & 15) == 0);
+  INK_CHECK_ARG(boxes && scores && keep && workspace_u64 && ink_aligned<16>(workspace_u64));
   const int nw = (n + 63) / 64;
   f32x4* sorted = (f32x4*)workspace_u64;                            // 2 n words
   u64* sup = (u64*)workspace_u64 + 2 * (int64_t)n;                  // n nw words
@@ -429,7 +429,7 @@ extern "C" int ink_mask_small_regions(const void* planes_u64, int32_t k, int32_t
                                       int32_t* changed, void* stream) {
   INK_CHECK_ARG(planes_u64 && tmp_planes_u64 && workspace && out_planes_u64 && changed && k > 0 && k <= 65535);
   INK_CHECK_ARG(H > 0 && W > 0 && H <= 16383 && W <= 16383 && min_area >= 0);
-  INK_CHECK_ARG((((uintptr_t)planes_u64 | (uintptr_t)tmp_planes_u64 | (uintptr_t)out_planes_u64 | (uintptr_t)workspace) & 7) == 0);
+  INK_CHECK_ARG(ink_aligned<8>(planes_u64, tmp_planes_u64, out_planes_u64, workspace));
   hipStream_t s = (hipStream_t)stream;
   const int Hp = (H + 63) / 64, R = W, RM = rsr_rm(H);
   const int64_t plane = (int64_t)W * Hp, stride = cc_ws_ints_per_plane(R, RM);

@@ -21,7 +21,7 @@
 //                   window partition / padding never materialises.
 // Streamed K/V (all other instances): 64-key tiles alternate between two LDS buffers, one barrier per tile.
 #include <stdlib.h>
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 int ink_win4_attn_launch(const InkAttn& p, int n_cus, hipStream_t s);   // attention_win.hip
@@ -29,24 +29,11 @@ int ink_glob4_attn_launch(const InkAttn& p, hipStream_t s);              // atte
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-__device__ __forceinline__ f16x4 tr_read(const char* p) {
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-  return __builtin_bit_cast(f16x4, v);
-}
-
 __device__ __forceinline__ f16x8 cvt8(const f32x16& s, int base) {
   f16x8 r;
 #pragma unroll
   for (int j = 0; j < 8; ++j) r[j] = (f16)s[base + j];
   return r;
-}
-
-__device__ __forceinline__ float max3(float a, float b, float c) {
-  float d;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
 }
 
 template <int HD, int MODE, int NW, bool ALLKV = false>
@@ -346,8 +333,8 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
       __builtin_amdgcn_sched_barrier(0);     // (the scheduler would sink the reads back next to their MFMAs)
     }
     if constexpr (MODE == 1) {
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfa[0], qf[0], rw0, 0, 0, 0);
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfb[0], qf[0], rw1, 0, 0, 0);
+      s0 = mfma32(kfa[0], qf[0], rw0);
+      s1 = mfma32(kfb[0], qf[0], rw1);
     } else if constexpr (MODE == 3) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -363,15 +350,15 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
 #pragma unroll
       for (int s = 0; s < NQK; ++s) {
         const f16x8 k0 = *(const f16x8*)(tK + koff0 + s * 32);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, qf[s], s0, 0, 0, 0);
+        s0 = mfma32(k0, qf[s], s0);
       }
     } else {
 #pragma unroll
       for (int s = (MODE == 1 ? 1 : 0); s < NQK; ++s) {
         const f16x8 k0 = KPRE ? kfa[s] : *(const f16x8*)(tK + koff0 + s * 32);
         const f16x8 k1 = KPRE ? kfb[s] : *(const f16x8*)(tK + koff1 + s * 32);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, qf[s], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, qf[s], s1, 0, 0, 0);
+        s0 = mfma32(k0, qf[s], s0);
+        s1 = mfma32(k1, qf[s], s1);
       }
     }
     if ((t + 1) * 64 > p.n_k) {  // ragged last tile: mask keys >= n_k (wave-uniform branch)
@@ -407,7 +394,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
       const f16x4 a0 = tr_read(base);
       const f16x4 a1 = tr_read(base + 8 * VROW);
       const f16x8 vf = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-      o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[ks], o[i], 0, 0, 0);
+      o[i] = mfma32(vf, pf[ks], o[i]);
     };
     if constexpr (LSUM_MFMA && !ALLKV) {
       // keys 0..31 first, and their P.V MFMAs go out while the exps of keys 32..63 are still being computed: an
@@ -564,7 +551,7 @@ __global__ __launch_bounds__(256) void relpos_mfma_kernel(const f16* __restrict_
 #pragma unroll
       for (int s = 0; s < HD / 16; ++s) {
         const f16x8 a = *(const f16x8*)(tab + (tt * 32 + lq) * TROW + (2 * s + hh) * 16);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[s], d, 0, 0, 0);
+        d = mfma32(a, qf[s], d);
       }
       const bool is_w = tt >= RT;
       const int base = (is_w ? qw : qh) + S - 1 - (tt % RT) * 32;   // j = base - (row within this tile)
@@ -617,8 +604,7 @@ extern "C" int ink_flash_attn(const InkAttn* pp, void* stream) {
   INK_CHECK_ARG(p.Q && p.K && p.V && p.O);
   INK_CHECK_ARG(p.n_batch > 0 && p.n_heads > 0 && p.n_q > 0 && p.n_k > 0);
   INK_CHECK_ARG(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 4 == 0);
-  INK_CHECK_ARG((((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V) & 15) == 0);
-  INK_CHECK_ARG(((uintptr_t)p.O & 7) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(p.Q, p.K, p.V) && ink_aligned<8>(p.O));
   INK_CHECK_ARG(!p.tok_rows || p.bias_mode == 2);
   static const int n_cus = [] {
     int dev = 0, n = 0;
@@ -633,9 +619,7 @@ extern "C" int ink_flash_attn(const InkAttn* pp, void* stream) {
     constexpr int nqk_ = HD / 16 + (MODE == 2 ? 2 : 0);                                                    \
     constexpr int lds_ = (ALL ? 4 : 2) * (64 * (((nqk_ * 2) | 1) * 16) + 64 * (((HD + 31) / 32) * 64)) +   \
                          0;                                                                            \
-    static bool attr_ = ((void)hipFuncSetAttribute((const void*)flash_attn_kernel<HD, MODE, NW, ALL>,      \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_), true); \
-    (void)attr_;                                                                                           \
+    ink_dyn_lds<flash_attn_kernel<HD, MODE, NW, ALL>>(lds_);                                               \
     const int nqb = (p.n_q + NW * 32 - 1) / (NW * 32);                                                     \
     const int grid_ = (ALL && persist) ? (bhn * nqb < n_cus ? bhn * nqb : n_cus) : bhn * nqb;                \
     hipLaunchKernelGGL((flash_attn_kernel<HD, MODE, NW, ALL>), dim3(grid_), dim3(NW * 64), lds_, s, p);      \
@@ -650,7 +634,7 @@ extern "C" int ink_flash_attn(const InkAttn* pp, void* stream) {
   } else if (p.head_dim == 80 && p.bias_mode == 2) {
     INK_CHECK_ARG(p.rel_aug && p.grid_w > 0 && p.grid_w <= 16 && p.n_k <= p.grid_w * p.grid_w && p.n_k <= 256);
     INK_CHECK_ARG(!p.tok_rows || (p.n_q == p.n_k && p.pad_k && p.pad_v &&
-                                  (((uintptr_t)p.pad_k | (uintptr_t)p.pad_v) & 15) == 0));
+                                  ink_aligned<16>(p.pad_k, p.pad_v)));
     // SAM's own window size (14 x 14 = 196 keys): the one-wave-per-SIMD kernel of attention_win.hip.  Its output
     // stores go through a 2 GiB buffer descriptor (invalid rows are dropped by the bounds check).
     if (p.n_k >= 193 && p.n_k <= 208 && p.n_q <= 256 &&
@@ -680,7 +664,7 @@ extern "C" int ink_relpos_bias64_f16(const void* Q, int64_t ldq, const float* re
                                      int32_t n_batch, int32_t n_heads, int32_t head_dim, float scale, void* out_h_f16,
                                      void* out_w_f16, void* stream) {
   INK_CHECK_ARG(Q && rel_pos_h && rel_pos_w && head_dim == 80 && ldq % 8 == 0 && out_h_f16 && out_w_f16);
-  INK_CHECK_ARG(n_batch > 0 && n_heads > 0 && scale > 0.f && ((((uintptr_t)out_h_f16 | (uintptr_t)out_w_f16) & 15) == 0));
+  INK_CHECK_ARG(n_batch > 0 && n_heads > 0 && scale > 0.f && ink_aligned<16>(out_h_f16, out_w_f16));
   hipLaunchKernelGGL((relpos_mfma_kernel<80, 64, false, true>), dim3(n_batch * n_heads * 16), dim3(256), 0, (hipStream_t)stream,
                      (const f16*)Q, ldq, rel_pos_h, rel_pos_w, n_heads, 1.0f / scale, (const int32_t*)nullptr,
                      (float*)out_h_f16, (float*)out_w_f16, (f16*)nullptr);

@@ -31,50 +31,12 @@
 // runs ~50 cycles longer than a bare MFMA gap; with none the tile takes 2050 (46 per MFMA, the LDS / load skeleton).
 // I.e. in this instruction stream the wave's own VALU does not hide under its MFMAs the way the guide's single-wave
 // measurements suggest; why (operand-port conflicts of 512-register waves? the volatile-asm pinning?) is open.
-#include <type_traits>
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f16x4 tr_read(const char* p) {
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-  return __builtin_bit_cast(f16x4, v);
-}
-__device__ __forceinline__ float max3(float a, float b, float c) {
-  float d;
-  asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-__device__ __forceinline__ float fma_at(float s, float c, float add) {
-  float t;
-  asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(s), "v"(c), "v"(add));
-  return t;
-}
-__device__ __forceinline__ float exp2_at(float t) {
-  float d;
-  asm volatile("v_exp_f32 %0, %1" : "=v"(d) : "v"(t));
-  return d;
-}
-__device__ __forceinline__ uint32_t cvt_pk_at(float a, float b) {
-  uint32_t d;
-  asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-__device__ __forceinline__ f32x16 mfma(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-template <int I> using ic = std::integral_constant<int, I>;
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ic<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 constexpr int HD = 80, NT = 256, NQK = 5, NB = 3, CH = 10;
 constexpr int KROW = 176, VROW = 192;                  // K rows: k | pad (odd chunk count); V rows: v | ones-column | pad
@@ -103,31 +65,31 @@ struct Sub {
 // j-th MFMA of an S unit (10): k-step j >> 1 on the lower (even j) / upper (odd j) 32 keys
 __device__ __forceinline__ void s_mfma(int j, const f16x8 (&kfa)[NQK], const f16x8 (&kfb)[NQK], Sub& u) {
   const int s = j >> 1;
-  if (j & 1) u.s1 = mfma(kfb[s], u.qf[s], u.s1);     // (s0 / s1 were preloaded with rel_w[q, kw])
-  else u.s0 = mfma(kfa[s], u.qf[s], u.s0);
+  if (j & 1) u.s1 = mfma32(kfb[s], u.qf[s], u.s1);     // (s0 / s1 were preloaded with rel_w[q, kw])
+  else u.s0 = mfma32(kfa[s], u.qf[s], u.s0);
 }
 __device__ __forceinline__ void pv_mfma(int j, const f16x8 (&vf)[12], Sub& u) {
-  u.o[j % 3] = mfma(vf[j], u.pfrag(j / 3), u.o[j % 3]);
+  u.o[j % 3] = mfma32(vf[j], u.pfrag(j / 3), u.o[j % 3]);
 }
 __device__ __forceinline__ void sm_max(int g, Sub& u) {
   if (g == 0) {
-    u.mx = max3(u.s0[0], u.s0[1], u.s0[2]);
-    u.mx2 = max3(u.s0[3], u.s0[4], u.s0[5]);
-    u.mx = max3(u.mx, u.s0[6], u.s0[7]);
-    u.mx2 = max3(u.mx2, u.s0[8], u.s0[9]);
-    u.mx = max3(u.mx, u.s0[10], u.s0[11]);
-    u.mx2 = max3(u.mx2, u.s0[12], u.s0[13]);
+    u.mx = max3_at(u.s0[0], u.s0[1], u.s0[2]);
+    u.mx2 = max3_at(u.s0[3], u.s0[4], u.s0[5]);
+    u.mx = max3_at(u.mx, u.s0[6], u.s0[7]);
+    u.mx2 = max3_at(u.mx2, u.s0[8], u.s0[9]);
+    u.mx = max3_at(u.mx, u.s0[10], u.s0[11]);
+    u.mx2 = max3_at(u.mx2, u.s0[12], u.s0[13]);
   } else if (g == 1) {
-    u.mx = max3(u.mx, u.s0[14], u.s0[15]);
-    u.mx2 = max3(u.mx2, u.s1[0], u.s1[1]);
-    u.mx = max3(u.mx, u.s1[2], u.s1[3]);
-    u.mx2 = max3(u.mx2, u.s1[4], u.s1[5]);
-    u.mx = max3(u.mx, u.s1[6], u.s1[7]);
+    u.mx = max3_at(u.mx, u.s0[14], u.s0[15]);
+    u.mx2 = max3_at(u.mx2, u.s1[0], u.s1[1]);
+    u.mx = max3_at(u.mx, u.s1[2], u.s1[3]);
+    u.mx2 = max3_at(u.mx2, u.s1[4], u.s1[5]);
+    u.mx = max3_at(u.mx, u.s1[6], u.s1[7]);
   } else {
-    u.mx2 = max3(u.mx2, u.s1[8], u.s1[9]);
-    u.mx = max3(u.mx, u.s1[10], u.s1[11]);
-    u.mx2 = max3(u.mx2, u.s1[12], u.s1[13]);
-    u.mx = max3(u.mx, u.s1[14], u.s1[15]);
+    u.mx2 = max3_at(u.mx2, u.s1[8], u.s1[9]);
+    u.mx = max3_at(u.mx, u.s1[10], u.s1[11]);
+    u.mx2 = max3_at(u.mx2, u.s1[12], u.s1[13]);
+    u.mx = max3_at(u.mx, u.s1[14], u.s1[15]);
     u.mx = fmaxf(u.mx, u.mx2);
   }
 }
@@ -433,11 +395,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // Launcher used by ink_flash_attn (attention.hip) for bias_mode 1.
 __attribute__((visibility("hidden"))) int ink_glob4_attn_launch(const InkAttn& p, hipStream_t s) {
-  static bool attr = ((void)hipFuncSetAttribute((const void*)glob4_attn_kernel<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES),
-                      (void)hipFuncSetAttribute((const void*)glob4_attn_kernel<true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), true);
-  (void)attr;
+  ink_dyn_lds<glob4_attn_kernel<false>>(LDS_BYTES);
+  ink_dyn_lds<glob4_attn_kernel<true>>(LDS_BYTES);
   const int grid = p.n_batch * p.n_heads * (p.n_q >> 8);
   if (p.rel_f16) {
     hipLaunchKernelGGL(glob4_attn_kernel<true>, dim3(grid), dim3(NT), LDS_BYTES, s, p);

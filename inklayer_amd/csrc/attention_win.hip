@@ -36,53 +36,12 @@
 // (336 MB of q,k,v,o: 2.75 TB/s = 34 % of 8 TB/s) against 172 us for the 2-waves-per-SIMD form; per block ~17 000
 // cycles of which 3 x 2450 are the tiles (52 MFMAs each: 47 cycles per gap, the gap's VALU + LDS + MFMA issue, not the
 // 32 of the MFMA pipe).
-#include <type_traits>
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 typedef int i32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f16x4 tr_read(const char* p) {
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-  return __builtin_bit_cast(f16x4, v);
-}
-// The softmax arithmetic is issued through VOLATILE asm statements: they keep their place between the sched_barriers of
-// the MFMA gaps.  As plain (pure) operations hipcc's instruction selection hoists them - e.g. all of a tile's second-half
-// exps into the gap that computes the row max - before the machine scheduler ever sees the barriers.
-__device__ __forceinline__ float max3(float a, float b, float c) {
-  float d;
-  asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-__device__ __forceinline__ float fma_at(float s, float c, float neg_m) {       // s c - m, pinned
-  float t;
-  asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(s), "v"(c), "v"(neg_m));
-  return t;
-}
-__device__ __forceinline__ float exp2_at(float t) {                             // 2^t, pinned
-  float d;
-  asm volatile("v_exp_f32 %0, %1" : "=v"(d) : "v"(t));
-  return d;
-}
-__device__ __forceinline__ uint32_t cvt_pk_at(float a, float b) {              // two f32 -> packed f16 (RNE), pinned
-  uint32_t d;
-  asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-__device__ __forceinline__ f32x16 mfma(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-template <int I> using ic = std::integral_constant<int, I>;
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ic<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 constexpr int HD = 80, NT = 256, NQKB = 5, NQK = 7, NB = 3, CH = 10;
 constexpr int KROW = 240, VROW = 192, ROWS = 232;     // K' rows: k | one-hot(kh, kw) | pad; V rows: v | ones-column | pad
@@ -114,40 +73,40 @@ struct Sub {
 __device__ __forceinline__ void s_mfma(int j, const f16x8 (&kfa)[NQK], const f16x8 (&kfb)[NQK], Sub& u) {
   const int s = j >> 1;
   const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (j & 1) u.s1 = mfma(kfb[s], u.qf[s], s == 0 ? z : u.s1);
-  else u.s0 = mfma(kfa[s], u.qf[s], s == 0 ? z : u.s0);
+  if (j & 1) u.s1 = mfma32(kfb[s], u.qf[s], s == 0 ? z : u.s1);
+  else u.s0 = mfma32(kfa[s], u.qf[s], s == 0 ? z : u.s0);
 }
 // k-step s of the tail tile's S unit (7): only the lower 32 keys exist
 __device__ __forceinline__ void s_mfma_tail(int s, const f16x8 (&kfa)[NQK], Sub& u) {
   const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  u.s0 = mfma(kfa[s], u.qf[s], s == 0 ? z : u.s0);
+  u.s0 = mfma32(kfa[s], u.qf[s], s == 0 ? z : u.s0);
 }
 // j-th MFMA of a full-tile PV unit (12): 16-key step j / 3, d-block j % 3
 __device__ __forceinline__ void pv_mfma(int j, const f16x8 (&vf)[12], Sub& u) {
-  u.o[j % 3] = mfma(vf[j], u.pfrag(j / 3), u.o[j % 3]);
+  u.o[j % 3] = mfma32(vf[j], u.pfrag(j / 3), u.o[j % 3]);
 }
 
 // ---- softmax, cut into MFMA-gap sized steps --------------------------------------------------------------------
 // max phase, gaps 0..2: 16 v_max3 over the 32 scores of the lane, as two independent chains
 __device__ __forceinline__ void sm_max(int g, Sub& u) {
   if (g == 0) {
-    u.mx = max3(u.s0[0], u.s0[1], u.s0[2]);
-    u.mx2 = max3(u.s0[3], u.s0[4], u.s0[5]);
-    u.mx = max3(u.mx, u.s0[6], u.s0[7]);
-    u.mx2 = max3(u.mx2, u.s0[8], u.s0[9]);
-    u.mx = max3(u.mx, u.s0[10], u.s0[11]);
-    u.mx2 = max3(u.mx2, u.s0[12], u.s0[13]);
+    u.mx = max3_at(u.s0[0], u.s0[1], u.s0[2]);
+    u.mx2 = max3_at(u.s0[3], u.s0[4], u.s0[5]);
+    u.mx = max3_at(u.mx, u.s0[6], u.s0[7]);
+    u.mx2 = max3_at(u.mx2, u.s0[8], u.s0[9]);
+    u.mx = max3_at(u.mx, u.s0[10], u.s0[11]);
+    u.mx2 = max3_at(u.mx2, u.s0[12], u.s0[13]);
   } else if (g == 1) {
-    u.mx = max3(u.mx, u.s0[14], u.s0[15]);
-    u.mx2 = max3(u.mx2, u.s1[0], u.s1[1]);
-    u.mx = max3(u.mx, u.s1[2], u.s1[3]);
-    u.mx2 = max3(u.mx2, u.s1[4], u.s1[5]);
-    u.mx = max3(u.mx, u.s1[6], u.s1[7]);
+    u.mx = max3_at(u.mx, u.s0[14], u.s0[15]);
+    u.mx2 = max3_at(u.mx2, u.s1[0], u.s1[1]);
+    u.mx = max3_at(u.mx, u.s1[2], u.s1[3]);
+    u.mx2 = max3_at(u.mx2, u.s1[4], u.s1[5]);
+    u.mx = max3_at(u.mx, u.s1[6], u.s1[7]);
   } else {
-    u.mx2 = max3(u.mx2, u.s1[8], u.s1[9]);
-    u.mx = max3(u.mx, u.s1[10], u.s1[11]);
-    u.mx2 = max3(u.mx2, u.s1[12], u.s1[13]);
-    u.mx = max3(u.mx, u.s1[14], u.s1[15]);
+    u.mx2 = max3_at(u.mx2, u.s1[8], u.s1[9]);
+    u.mx = max3_at(u.mx, u.s1[10], u.s1[11]);
+    u.mx2 = max3_at(u.mx2, u.s1[12], u.s1[13]);
+    u.mx = max3_at(u.mx, u.s1[14], u.s1[15]);
     u.mx = fmaxf(u.mx, u.mx2);
   }
 }
@@ -213,9 +172,9 @@ __device__ __forceinline__ void sm_tail(Sub& u, float c, int n_k, int hh) {
     const int key = 192 + (r & 3) + 8 * (r >> 2) + 4 * hh;
     if (key >= n_k) u.s0[r] = NEG;
   }
-  u.mx = max3(u.s0[0], u.s0[1], u.s0[2]);
-  u.mx = max3(u.mx, u.s0[3], u.s0[4]);
-  u.mx = max3(u.mx, u.s0[5], u.s0[6]);
+  u.mx = max3_at(u.s0[0], u.s0[1], u.s0[2]);
+  u.mx = max3_at(u.mx, u.s0[3], u.s0[4]);
+  u.mx = max3_at(u.mx, u.s0[5], u.s0[6]);
   u.mx = fmaxf(u.mx, u.s0[7]);
   sm_decide<false>(u, c);
   float f[8];
@@ -548,10 +507,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         GAP();
       });
 #pragma unroll
-      for (int i = 0; i < NB; ++i) A.o[i] = mfma(vt[i], A.pfrag(0), A.o[i]);
+      for (int i = 0; i < NB; ++i) A.o[i] = mfma32(vt[i], A.pfrag(0), A.o[i]);
       sm_tail(B, c, p.n_k, hh);
 #pragma unroll
-      for (int i = 0; i < NB; ++i) B.o[i] = mfma(vt[i], B.pfrag(0), B.o[i]);
+      for (int i = 0; i < NB; ++i) B.o[i] = mfma32(vt[i], B.pfrag(0), B.o[i]);
     }
 #undef GAP
 
@@ -597,11 +556,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // Launcher used by ink_flash_attn (attention.hip) for bias_mode 2 at SAM's window size.
 __attribute__((visibility("hidden"))) int ink_win4_attn_launch(const InkAttn& p, int n_cus, hipStream_t s) {
-  static bool attr = ((void)hipFuncSetAttribute((const void*)win4_attn_kernel<true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES),
-                      (void)hipFuncSetAttribute((const void*)win4_attn_kernel<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), true);
-  (void)attr;
+  ink_dyn_lds<win4_attn_kernel<true>>(LDS_BYTES);
+  ink_dyn_lds<win4_attn_kernel<false>>(LDS_BYTES);
   const int bhn = p.n_batch * p.n_heads;
   const int grid = bhn < n_cus ? bhn : n_cus;            // persistent walk over (window, head) blocks
   if (p.tok_rows) {

@@ -366,8 +366,7 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
   INK_CHECK_ARG(io_f32 == 0 || io_f32 == 1);
   // every kernel moves 16-byte vectors: with ld % 8 == 0 an aligned base keeps every row aligned
-  INK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) == 0);
-  INK_CHECK_ARG(!q_add || (((uintptr_t)q_add & 15) == 0));
+  INK_CHECK_ARG(ink_aligned<16>(Q, K, V, O, q_add));
   const int64_t total = (int64_t)B * n_q * n_heads;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
@@ -404,15 +403,11 @@ extern "C" int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t 
   INK_CHECK_ARG(Q && K && V && O && n_batch > 0 && n_q > 0 && n_q <= 16 && n_k > 0 && n_heads > 0);
   INK_CHECK_ARG(head_dim == 16 && n_heads % 4 == 0);
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
-  INK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) == 0);   // 16-byte loads and stores
-  INK_CHECK_ARG(!k_add || ((uintptr_t)k_add & 15) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(Q, K, V, O, k_add));   // 16-byte loads and stores
   // two key-range groups x (K, V) tiles of 64 keys x 4 heads x 16 f32; at 4 queries per wave also the scaled queries
   constexpr int lds2 = 2 * 2 * 64 * 64 * 4, lds4 = lds2 + 16 * 64 * 4;
-  static bool attr = ((void)hipFuncSetAttribute((const void*)attn_fewq16_kernel<2>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds2),
-                      (void)hipFuncSetAttribute((const void*)attn_fewq16_kernel<4>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds4), true);
-  (void)attr;
+  ink_dyn_lds<attn_fewq16_kernel<2>>(lds2);
+  ink_dyn_lds<attn_fewq16_kernel<4>>(lds4);
   const bool wide = n_q > 8;                            // 9..16 queries: 4 per wave
   hipLaunchKernelGGL(wide ? attn_fewq16_kernel<4> : attn_fewq16_kernel<2>, dim3(n_batch * (n_heads / 4)), dim3(512),
                      wide ? lds4 : lds2, (hipStream_t)stream, (const float*)Q, ldq, (const float*)K, ldk,

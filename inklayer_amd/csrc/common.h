@@ -27,6 +27,23 @@ static inline int ink_launch_status() {
   return e == hipSuccess ? INK_OK : INK_ERR_LAUNCH;
 }
 
+// True if every pointer is a multiple of N bytes (a power of two); null passes, as an optional argument must.  Every
+// pointer a kernel reads or writes with N-byte vector accesses belongs in the launcher's check: a forgotten one is a
+// misaligned access on the device.
+template <unsigned N, class... P>
+static inline bool ink_aligned(const P*... p) {
+  static_assert(N && !(N & (N - 1)), "alignment is a power of two");
+  return ((... | (uintptr_t)p) & (N - 1)) == 0;
+}
+
+// Once-only opt-in of KERNEL to `bytes` of dynamic LDS (above 64 KiB a launch fails without it): one flag per kernel.
+template <auto KERNEL>
+static inline void ink_dyn_lds(int bytes) {
+  static bool done =
+      ((void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), true);
+  (void)done;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -52,6 +69,28 @@ __device__ __forceinline__ float gelu_erf(float x) {
   pl = fmaf(pl, t, 0.254829592f);
   const float e = pl * t * __builtin_amdgcn_exp2f(-(u * u));           // 1 - erf(|x| / sqrt 2)
   return fmaf(-0.5f * fabsf(x), e, fmaxf(x, 0.0f));
+}
+
+// Split-f16 operand: an f32 value v travels into an f16 MFMA GEMM as THREE K-segments
+//   [ hi | lo * 64 | hi / 64 ],  hi = f16(v), lo = v - hi,
+// against weights that ops.split_weight lays out as [ W_hi | W_hi / 64 | W_lo * 64 ], so the accumulator receives
+// hi W_hi + lo W_hi + hi W_lo = v W to ~2^-21 relative.  Both sides must use the SAME scale; 64 because it is a power
+// of two (exact) that keeps both low parts inside f16's NORMAL range for |v|, |W| >= 4e-3 (no reliance on how the MFMA
+// unit treats f16 subnormals).
+__device__ __forceinline__ void split_f16(float v, f16& hi, f16& lo, f16& hs) {
+  const f16 h = (f16)v;     // (a local: the three outputs may be neighbours in memory)
+  hi = h;
+  lo = (f16)((v - (float)h) * 64.0f);
+  hs = (f16)((float)h * 0.015625f);
+}
+// four values as the three segments of a row whose segments are C halves apart
+__device__ __forceinline__ void split_store(f16* o, int C, const f32x4& y) {
+  f16 hi[4], lo[4], hs[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) split_f16(y[e], hi[e], lo[e], hs[e]);
+  *(f16x4*)o = (f16x4){hi[0], hi[1], hi[2], hi[3]};
+  *(f16x4*)(o + C) = (f16x4){lo[0], lo[1], lo[2], lo[3]};
+  *(f16x4*)(o + 2 * C) = (f16x4){hs[0], hs[1], hs[2], hs[3]};
 }
 
 // RGB -> grey of 8-bit pixels: the three fixed-point forms of (0.299, 0.587, 0.114) that the reference's libraries

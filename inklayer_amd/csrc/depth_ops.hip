@@ -64,6 +64,8 @@ __global__ __launch_bounds__(256) void depth_patchify_kernel(const uint8_t* __re
     }
   }
   const float f = (float)((v - nrm.mean[c]) / nrm.std[c]);
+  // split_f16 (common.h) written out: each segment is stored before the next is computed, and hipcc's schedule of the
+  // whole kernel follows that order (see profiles/scaffolding_isa.txt)
   const f16 hi = (f16)f;
   o[0] = hi;
   o[KP] = (f16)((f - (float)hi) * 64.0f);

@@ -553,11 +553,8 @@ extern "C" int ink_topk_rowmax(const float* logits, int32_t B, int32_t S, int32_
   const int nchunk = (S + CHUNK - 1) / CHUNK;
   INK_CHECK_ARG(nchunk == 1 || (cand_ws && K <= CHUNK / 2 && S - (nchunk - 1) * CHUNK >= 0 && nchunk * K <= 16384));
   INK_CHECK_ARG(nchunk == 1 || S / nchunk >= K);   // every chunk must hold at least K tokens
-  static bool attr = ((void)hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                CHUNK * 8),
-                      (void)hipFuncSetAttribute((const void*)topk_merge_kernel,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * 8), true);
-  (void)attr;
+  ink_dyn_lds<topk_kernel>(CHUNK * 8);
+  ink_dyn_lds<topk_merge_kernel>(CHUNK * 8);
   hipStream_t s = (hipStream_t)stream;
   // equal chunks so that each one has >= K tokens
   const int chunk = (S + nchunk - 1) / nchunk;

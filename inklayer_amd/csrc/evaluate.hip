@@ -361,9 +361,8 @@ __global__ __launch_bounds__(256) void eval_paint_kernel(const uint16_t* __restr
   }
 }
 
-static inline bool eval_al(const void* q, unsigned bytes) { return ((uintptr_t)q & (bytes - 1u)) == 0; }
 static inline bool eval_dims_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31); }
-static inline bool eval_rank_ok(const void* rank, int U) { return rank && eval_al(rank, 2) && U >= 1 && U <= EVAL_MAX_U; }
+static inline bool eval_rank_ok(const void* rank, int U) { return rank && ink_aligned<2>(rank) && U >= 1 && U <= EVAL_MAX_U; }
 // workgroups of a grid-stride pass: two steps of 1024 pixels each where the image has them, at most 1024 workgroups
 static inline unsigned eval_strips(int64_t npix) {
   const int64_t chunks = (npix + EVAL_CHUNK - 1) / EVAL_CHUNK;
@@ -376,14 +375,16 @@ static inline unsigned eval_strips(int64_t npix) {
 extern "C" int ink_eval_label_ranks(const void* labels, int32_t elem_size, int32_t H, int32_t W, uint32_t* workspace,
                                     int32_t* values, int32_t values_cap, int32_t* info, uint16_t* rank, void* stream) {
   INK_CHECK_ARG(labels && workspace && values && info && rank && eval_dims_ok(H, W));
-  INK_CHECK_ARG((elem_size == 1 || elem_size == 2 || elem_size == 4) && values_cap >= 1 && eval_al(rank, 2));
+  INK_CHECK_ARG((elem_size == 1 || elem_size == 2 || elem_size == 4) && values_cap >= 1 && ink_aligned<2>(rank));
   hipStream_t s = (hipStream_t)stream;
   const int64_t npix = (int64_t)H * W;
   uint32_t* bitmap = workspace;
   uint32_t* prefix = workspace + EVAL_BITMAP_WORDS;
   if (hipMemsetAsync(bitmap, 0, EVAL_BITMAP_WORDS * sizeof(uint32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   if (hipMemsetAsync(info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
-  const int aligned = (eval_al(labels, 4u * (unsigned)elem_size) ? EVAL_AL_LABELS : 0) | (eval_al(rank, 8) ? EVAL_AL_RANK : 0);
+  const bool labels4 =      // four labels per load
+      elem_size == 1 ? ink_aligned<4>(labels) : elem_size == 2 ? ink_aligned<8>(labels) : ink_aligned<16>(labels);
+  const int aligned = (labels4 ? EVAL_AL_LABELS : 0) | (ink_aligned<8>(rank) ? EVAL_AL_RANK : 0);
   hipLaunchKernelGGL(eval_presence_kernel, dim3(eval_strips(npix)), dim3(256), 0, s, labels, elem_size, npix, aligned,
                      bitmap, info);
   hipLaunchKernelGGL(eval_prefix_kernel, dim3(1), dim3(256), 0, s, (const uint32_t*)bitmap, prefix, values, values_cap, info);
@@ -401,8 +402,8 @@ extern "C" int ink_eval_contingency(const void* pred_u8, int32_t n, int32_t by_l
   hipStream_t s = (hipStream_t)stream;
   const int64_t npix = (int64_t)H * W;
   if (hipMemsetAsync(table, 0, (size_t)(n + 1) * U * sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
-  int aligned = (eval_al(rank_u16, 8) ? EVAL_AL_RANK : 0) | (eval_al(sketch_u8, 4) ? EVAL_AL_SKETCH : 0);
-  if (eval_al(pred_u8, 4) && (by_label || (npix & 3) == 0)) aligned |= EVAL_AL_PRED;
+  int aligned = (ink_aligned<8>(rank_u16) ? EVAL_AL_RANK : 0) | (ink_aligned<4>(sketch_u8) ? EVAL_AL_SKETCH : 0);
+  if (ink_aligned<4>(pred_u8) && (by_label || (npix & 3) == 0)) aligned |= EVAL_AL_PRED;
   const unsigned tiles = (unsigned)((n + 1 + EVAL_TILE - 1) / EVAL_TILE);
   hipLaunchKernelGGL(eval_contingency_kernel, dim3(eval_strips(npix), tiles), dim3(256), 0, s, (const uint8_t*)pred_u8, n,
                      by_label ? 1 : 0, (const uint16_t*)rank_u16, U, stroke_only ? (const uint8_t*)sketch_u8 : nullptr,
@@ -416,7 +417,7 @@ extern "C" int ink_eval_label_boxes(const void* rank_u16, int32_t U, int32_t H, 
   const int64_t npix = (int64_t)H * W;
   hipLaunchKernelGGL(eval_boxes_init_kernel, dim3((unsigned)((4 * U + 255) / 256)), dim3(256), 0, s, boxes, U);
   hipLaunchKernelGGL(eval_boxes_kernel, dim3(eval_strips(npix)), dim3(256), 0, s, (const uint16_t*)rank_u16, U, W, npix,
-                     eval_al(rank_u16, 8) ? EVAL_AL_RANK : 0, boxes);
+                     ink_aligned<8>(rank_u16) ? EVAL_AL_RANK : 0, boxes);
   return ink_launch_status();
 }
 
@@ -424,7 +425,7 @@ extern "C" int ink_eval_paint_labels(const void* rank_u16, const void* colors_u8
                                      void* out_rgb_u8, void* stream) {
   INK_CHECK_ARG(colors_u8 && out_rgb_u8 && eval_rank_ok(rank_u16, U) && eval_dims_ok(H, W));
   const int64_t npix = (int64_t)H * W;
-  const int aligned = (eval_al(rank_u16, 8) ? EVAL_AL_RANK : 0) | (eval_al(out_rgb_u8, 4) ? EVAL_AL_OUT : 0);
+  const int aligned = (ink_aligned<8>(rank_u16) ? EVAL_AL_RANK : 0) | (ink_aligned<4>(out_rgb_u8) ? EVAL_AL_OUT : 0);
   hipLaunchKernelGGL(eval_paint_kernel, dim3((unsigned)((npix + EVAL_CHUNK - 1) / EVAL_CHUNK)), dim3(256), 0,
                      (hipStream_t)stream, (const uint16_t*)rank_u16, (const uint8_t*)colors_u8, U, npix, aligned,
                      (uint8_t*)out_rgb_u8);

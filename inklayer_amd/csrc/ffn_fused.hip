@@ -21,14 +21,10 @@
 //   * Epilogue: a lane holds half of its row (128 values), the other half sits in lane ^ 32: LayerNorm statistics are
 //     in-lane sums + one cross-half exchange; rows leave through LDS (the weight buffers are free by then) as whole
 //     1-KiB rows.
-#include <type_traits>
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int C = 256, HC = 64, BM = 128;
 constexpr int BLK = 1024;                       // one A-operand block: 32 rows x 16 k of f16, lane-linear
@@ -47,45 +43,6 @@ constexpr int NSLOT = (NBLK + 3) / 4;           // LDS-DMA pieces per wave and c
 static_assert(4 * 32 * OROW <= 2 * CHUNK, "epilogue staging fits the (then free) weight buffers");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-typedef __attribute__((address_space(3))) char* lds_char_ptr;
-template <int I> using ic = std::integral_constant<int, I>;
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ic<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-// Fragment reads are volatile asm so that they KEEP their distance to the MFMA that consumes them (left to itself hipcc
-// sinks every ds_read next to its use and waits lgkmcnt(0) in front of each MFMA: 6000 instead of 2100 cycles per chunk);
-// the counted wait is tied to the fragment it releases, which orders the MFMA behind it.  Nothing else in the loop uses
-// lgkmcnt, and LDS returns in order.
-template <int OFF>
-__device__ __forceinline__ f16x8 lds_frag(uint32_t addr) {
-  f16x8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_frag(f16x8& f) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(N));
-}
-// four parameter vectors (2 x gamma, 2 x beta of one 8-column group pair) through the same pinned path: as plain loads
-// hipcc puts all 64 of a LayerNorm in flight at once (256 registers) and spills - and a spilled fragment register of the
-// asm reads above would be stored before its data has arrived
-template <int OFF>
-__device__ __forceinline__ f32x4 lds_f4(uint32_t addr) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ void wait_f4(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-
-__device__ __forceinline__ f32x16 mfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 // position p = 8 hh + e of a 16-wide k-step of phase B  <->  hidden unit (within the 16-block) the lane holds there
 __host__ __device__ constexpr int hid_perm(int p) { return (p & 7) < 4 ? 4 * (p >> 3) + (p & 7) : 8 + 4 * (p >> 3) + (p & 7) - 4; }
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(256) void ffn256_fused_kernel(const f16* __restrict
 
   // LayerNorm over the 256 columns of the lane's row, in the accumulators: 128 values here, 128 in lane ^ 32; gamma / beta
   // from the LDS strip (which = 0: pre_g / pre_be, 3: ln_g / ln_b), two 4-column groups at a time
-  const uint32_t par0 = (uint32_t)(uintptr_t)(lds_char_ptr)smem + 2 * CHUNK + 16 * hh;
+  const uint32_t par0 = lds_addr(smem) + 2 * CHUNK + 16 * hh;
   auto layernorm = [&](int which) {
     float sum = 0.f;
 #pragma unroll
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(256) void ffn256_fused_kernel(const f16* __restrict
     });
   };
 
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_ptr)smem + lane * 16;
+  const uint32_t lds0 = lds_addr(smem) + lane * 16;
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if constexpr (PRE) {
     // a loop of its own (as a branch inside the chunk loop below it made hipcc park half of the main loop's state in
@@ -363,7 +320,7 @@ extern "C" int ink_ffn256_pack_bytes(int32_t hid, int32_t with_pre, int64_t* out
 extern "C" int ink_ffn256_pack(const void* w1_f16, const float* b1, const void* w2_f16, int32_t hid, const void* wpre_f16,
                                void* blob, void* stream) {
   INK_CHECK_ARG(w1_f16 && b1 && w2_f16 && blob && hid > 0 && hid % HC == 0 && hid <= MAX_HID);
-  INK_CHECK_ARG((((uintptr_t)w1_f16 | (uintptr_t)blob | (uintptr_t)wpre_f16) & 15) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(w1_f16, blob, wpre_f16));
   const int64_t pieces = (int64_t)((wpre_f16 ? NPRE : 0) + hid / HC) * NBLK * 64;
   hipLaunchKernelGGL(ffn256_pack_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const f16*)w1_f16, b1, (const f16*)w2_f16, hid, (const f16*)wpre_f16, (f16*)blob);
@@ -377,13 +334,9 @@ extern "C" int ink_ffn256_fused(const void* x_f16, int64_t ldx, const float* res
   INK_CHECK_ARG(x_f16 && res_f32 && blob && b2 && ln_g && ln_b && out_f32);
   INK_CHECK_ARG(M > 0 && hid > 0 && hid % HC == 0 && hid <= MAX_HID && ldx >= C && ldx % 8 == 0);
   INK_CHECK_ARG((!pre_bias && !pre_ln_g && !pre_ln_b) || (pre_bias && pre_ln_g && pre_ln_b));
-  INK_CHECK_ARG((((uintptr_t)x_f16 | (uintptr_t)res_f32 | (uintptr_t)blob | (uintptr_t)b2 | (uintptr_t)ln_g |
-                  (uintptr_t)ln_b | (uintptr_t)out_f32 | (uintptr_t)pre_bias | (uintptr_t)pre_ln_g | (uintptr_t)pre_ln_b) & 15) == 0);
-  static bool attr = ((void)hipFuncSetAttribute((const void*)ffn256_fused_kernel<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES),
-                      (void)hipFuncSetAttribute((const void*)ffn256_fused_kernel<true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), true);
-  (void)attr;
+  INK_CHECK_ARG(ink_aligned<16>(x_f16, res_f32, blob, b2, ln_g, ln_b, out_f32, pre_bias, pre_ln_g, pre_ln_b));
+  ink_dyn_lds<ffn256_fused_kernel<false>>(LDS_BYTES);
+  ink_dyn_lds<ffn256_fused_kernel<true>>(LDS_BYTES);
   const int ntiles = (M + BM - 1) / BM;
   if (pre_bias) {
     hipLaunchKernelGGL(ffn256_fused_kernel<true>, dim3(ntiles), dim3(256), LDS_BYTES, (hipStream_t)stream, (const f16*)x_f16,

@@ -20,7 +20,7 @@
 // Tile choice: ink_gemm_query_variant (shape heuristic); ink_gemm_set_variant forces one of its tile families (tests).
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
@@ -32,9 +32,6 @@ template <> struct Swz<64> {  // 128-B rows, 8 chunks
 template <> struct Swz<32> {  // 64-B rows, 4 chunks
   static __device__ __forceinline__ int f(int row) { return (-(row >> 2)) & 3; }
 };
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // ---------------------------------------------------------------------------------------------------------
 // Accumulator set-up and epilogue of one wave tile (TM x TN MFMA tiles of 16x16; the lane holds
@@ -490,9 +487,7 @@ static int launch_gemm_pp(const InkGemm& p, hipStream_t s, int group_m) {
   constexpr int BN = 64 * PP_TN;
   constexpr int lds = PP_RING * (256 + BN) * 32 * 2;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt_pp,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
-  (void)attr;
+  ink_dyn_lds<gemm_f16_nt_pp>(lds);
   const int ntiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
   hipLaunchKernelGGL(gemm_f16_nt_pp, dim3(ntiles), dim3(512), lds, s, p, group_m);
   return ink_launch_status();
@@ -502,9 +497,7 @@ template <int BM, int BN, int BK, int WM, int WN>
 static int launch_gemm(const InkGemm& p, hipStream_t s, int group_m = 1) {
   constexpr int lds = NS * (BM + BN) * BK * 2;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr = ((void)hipFuncSetAttribute((const void*)gemm_f16_nt<BM, BN, BK, WM, WN>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
-  (void)attr;
+  ink_dyn_lds<gemm_f16_nt<BM, BN, BK, WM, WN>>(lds);
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   hipLaunchKernelGGL((gemm_f16_nt<BM, BN, BK, WM, WN>), dim3(ntm * ntn), dim3(WM * WN * 64), lds, s, p, group_m);
   return ink_launch_status();
@@ -660,9 +653,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16_nt(InkGemm p, ConvGeom g) {
 template <int BK, bool RELU_IN>
 static int launch_conv3x3(const InkGemm& p, const ConvGeom& g, hipStream_t s) {
   constexpr int lds = NS * (128 + 128) * BK * 2;
-  static bool attr = ((void)hipFuncSetAttribute((const void*)conv3x3_f16_nt<BK, RELU_IN>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
-  (void)attr;
+  ink_dyn_lds<conv3x3_f16_nt<BK, RELU_IN>>(lds);
   const int ntm = (p.M + 127) / 128, ntn = (p.N + 127) / 128;
   hipLaunchKernelGGL((conv3x3_f16_nt<BK, RELU_IN>), dim3(ntm * ntn), dim3(256), lds, s, p, g);
   return ink_launch_status();
@@ -677,8 +668,7 @@ extern "C" int ink_conv3x3_f16(const void* in_f16, int32_t B, int32_t H, int32_t
   INK_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
   INK_CHECK_ARG(C % 32 == 0 && N % 4 == 0);
   INK_CHECK_ARG(stride == 1 || stride == 2);
-  INK_CHECK_ARG(((uintptr_t)in_f16 & 15) == 0 && ((uintptr_t)wt_f16 & 15) == 0);
-  INK_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)residual & 15) == 0 && ((uintptr_t)bias & 15) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(in_f16, wt_f16, out, residual, bias));
   INK_CHECK_ARG(relu_in == 0 || relu_in == 1);
   INK_CHECK_ARG(act == INK_ACT_NONE || act == INK_ACT_RELU);
   INK_CHECK_ARG(out_f16 == 0 || out_f16 == 1);
@@ -733,8 +723,7 @@ extern "C" int ink_gemm_f16(const InkGemm* pp, void* stream) {
   INK_CHECK_ARG(p.lda % 8 == 0 && p.ldw % 8 == 0 && p.lda >= p.K && p.ldw >= p.K);
   INK_CHECK_ARG(p.ldc % 4 == 0 && p.ldc >= p.N);
   INK_CHECK_ARG(!p.residual || (p.ldr % 4 == 0 && p.ldr >= p.N));
-  INK_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.W & 15) == 0);
-  INK_CHECK_ARG(((uintptr_t)p.C & 15) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(p.A, p.W, p.C));
   INK_CHECK_ARG(p.act >= 0 && p.act <= 2);
   INK_CHECK_ARG(p.c_f16 == 0 || p.c_f16 == 1);
   hipStream_t s = (hipStream_t)stream;

@@ -29,9 +29,11 @@ __global__ __launch_bounds__(256) void sam_patchify_kernel(const uint8_t* __rest
       const int x = x0 + j;
       float f = 0.f;  // padded area is zero AFTER normalisation (SA/modeling/sam.py:167-173)
       if (y < h && x < w) f = ((float)img[((int64_t)y * w + x) * 3 + cs] - mean_is[c]) * istd[c];
-      v[j] = (f16)f;
-      lo[j] = (f16)((f - (float)v[j]) * 64.0f);      // split-f16 operand segments, see ink_add_split_f16
-      hs[j] = (f16)((float)v[j] * 0.015625f);
+      f16 a, b, d;
+      split_f16(f, a, b, d);
+      v[j] = a;
+      lo[j] = b;
+      hs[j] = d;
     }
     if (split) {
       f16* o = out + (int64_t)tok * 3 * KP + col;

@@ -353,7 +353,7 @@ int launch_fwd(const void* value, const void* loc, const void* aw, Levels lv, in
 template <typename T, int NVMAX, typename Levels>
 int dispatch_fwd(const void* value, const void* loc, const void* aw, Levels lv, int B, int S, int M, int C, int Q,
                  int L, int P, void* out, hipStream_t s) {
-  const bool aligned = (((uintptr_t)value | (uintptr_t)out) & 15) == 0;
+  const bool aligned = ink_aligned<16>(value, out);
   if (aligned && C % NVMAX == 0) return launch_fwd<T, NVMAX>(value, loc, aw, lv, B, S, M, C, Q, L, P, out, s);
   if (aligned && C % (NVMAX / 2) == 0) return launch_fwd<T, NVMAX / 2>(value, loc, aw, lv, B, S, M, C, Q, L, P, out, s);
   return launch_fwd<T, 1>(value, loc, aw, lv, B, S, M, C, Q, L, P, out, s);

@@ -4,24 +4,6 @@
 
 namespace {
 
-// Split-f16 operands: an f32 value v travels into an f16 MFMA GEMM as THREE K-segments
-//   [ hi | (v - hi) * 64 | hi / 64 ],  hi = f16(v),
-// against weights laid out as [ W_hi | W_hi / 64 | (W - W_hi) * 64 ], so the accumulator receives
-// hi*W_hi + lo*W_hi + hi*W_lo = v*W to ~2^-21 relative.  The powers of two keep both low parts inside f16's
-// NORMAL range for |v|, |W| >= 4e-3 (no reliance on how the MFMA unit treats f16 subnormals).
-__device__ __forceinline__ void split_store(f16* o, int C, const f32x4& y) {
-  f16x4 hi, lo, hs;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    hi[e] = (f16)y[e];
-    lo[e] = (f16)((y[e] - (float)hi[e]) * 64.0f);
-    hs[e] = (f16)((float)hi[e] * 0.015625f);
-  }
-  *(f16x4*)o = hi;
-  *(f16x4*)(o + C) = lo;
-  *(f16x4*)(o + 2 * C) = hs;
-}
-
 // one wave per output row; row kept in registers (C <= 2048 -> <= 8 float4 per lane)
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(

@@ -11,15 +11,10 @@
 // weight: 192 one-KiB operand blocks = three 64-KiB chunks, one per segment, streamed by LDS-DMA through two buffers
 // (straight-line: no chunk loop).  LayerNorm in the accumulators; rows leave through a wave-private LDS tile as whole
 // 1-KiB f32 rows and 512-B f16 segments.
-#include <type_traits>
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) char* lds_char_ptr;
 
 constexpr int CI = 128, C = 256, BM = 128;
 constexpr int BLK = 1024;
@@ -32,38 +27,6 @@ constexpr int PAR_OFF = 4 * 32 * OROW;               // the parameter strip sits
 constexpr int LDS_BYTES = PAR_OFF + PAR_BYTES;
 constexpr int DEPTH = 4;
 static_assert(PAR_OFF >= 2 * CHUNK && LDS_BYTES <= 160 * 1024, "LDS layout");
-
-template <int I> using ic = std::integral_constant<int, I>;
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ic<I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-__device__ __forceinline__ f32x16 mfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// pinned LDS reads with counted waits tied to the value they release (see ffn_fused.hip)
-template <int OFF>
-__device__ __forceinline__ f16x8 lds_frag(uint32_t addr) {
-  f16x8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_frag(f16x8& f) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(N));
-}
-template <int OFF>
-__device__ __forceinline__ f32x4 lds_f4(uint32_t addr) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ void wait_f4(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
 
 // ws f16 [256, 384] (ops.split_weight layout) -> blob [3 segments][64 blocks][64 lanes][8]
 __global__ __launch_bounds__(256) void proj_ln_pack_kernel(const f16* __restrict__ ws, f16* __restrict__ blob) {
@@ -102,10 +65,11 @@ __global__ __launch_bounds__(256) void proj256_ln_kernel(const float* __restrict
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float v = e < 4 ? a0[e] : a1[e - 4];
-        const f16 hi = (f16)v;
+        f16 hi, lo, hs;
+        split_f16(v, hi, lo, hs);
         xf[s][e] = hi;
-        xf[KSEG + s][e] = (f16)((v - (float)hi) * 64.0f);
-        xf[2 * KSEG + s][e] = (f16)((float)hi * 0.015625f);
+        xf[KSEG + s][e] = lo;
+        xf[2 * KSEG + s][e] = hs;
       }
     }
   }
@@ -137,8 +101,8 @@ __global__ __launch_bounds__(256) void proj256_ln_kernel(const float* __restrict
   };
 #pragma unroll
   for (int k = 0; k < NBLK / 4; ++k) stage(0, 0, k);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_ptr)smem + lane * 16;
-  const uint32_t par0 = (uint32_t)(uintptr_t)(lds_char_ptr)smem + PAR_OFF + 16 * hh;
+  const uint32_t lds0 = lds_addr(smem) + lane * 16;
+  const uint32_t par0 = lds_addr(smem) + PAR_OFF + 16 * hh;
 
   static_for<0, NSEG>([&](auto cc) {
     constexpr int seg = decltype(cc)::value;
@@ -216,17 +180,13 @@ __global__ __launch_bounds__(256) void proj256_ln_kernel(const float* __restrict
     const f32x4 v = *(const f32x4*)(ot + r * OROW + lane * 16);
     if (out_f32) *(f32x4*)(out_f32 + m * C + lane * 4) = v;
     if (out_split) {
-      f16x4 hi, lo, hs;
+      f16 hi[4], lo[4], hs[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (f16)v[e];
-        lo[e] = (f16)((v[e] - (float)hi[e]) * 64.0f);
-        hs[e] = (f16)((float)hi[e] * 0.015625f);
-      }
+      for (int e = 0; e < 4; ++e) split_f16(v[e], hi[e], lo[e], hs[e]);
       f16* o = out_split + m * (3 * C) + lane * 4;
-      *(f16x4*)o = hi;
-      *(f16x4*)(o + C) = lo;
-      *(f16x4*)(o + 2 * C) = hs;
+      *(f16x4*)o = (f16x4){hi[0], hi[1], hi[2], hi[3]};
+      *(f16x4*)(o + C) = (f16x4){lo[0], lo[1], lo[2], lo[3]};
+      *(f16x4*)(o + 2 * C) = (f16x4){hs[0], hs[1], hs[2], hs[3]};
     }
   }
 }
@@ -234,7 +194,7 @@ __global__ __launch_bounds__(256) void proj256_ln_kernel(const float* __restrict
 }  // namespace
 
 extern "C" int ink_proj256_ln_pack(const void* ws_f16, void* blob_f16, void* stream) {
-  INK_CHECK_ARG(ws_f16 && blob_f16 && ((((uintptr_t)ws_f16 | (uintptr_t)blob_f16) & 15) == 0));
+  INK_CHECK_ARG(ws_f16 && blob_f16 && ink_aligned<16>(ws_f16, blob_f16));
   hipLaunchKernelGGL(proj_ln_pack_kernel, dim3((NSEG * NBLK * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const f16*)ws_f16, (f16*)blob_f16);
   return ink_launch_status();
@@ -245,11 +205,8 @@ extern "C" int ink_proj256_ln(const float* a_f32, const void* blob_f16, const fl
                               float eps, int64_t rows, float* out_f32, void* out_split_f16, void* stream) {
   INK_CHECK_ARG(a_f32 && blob_f16 && bias && res_f32 && ln_g && ln_b && rows > 0 && (out_f32 || out_split_f16));
   INK_CHECK_ARG(!res_batch_rows || (rows_per_batch > 0 && rows % rows_per_batch == 0));
-  INK_CHECK_ARG((((uintptr_t)a_f32 | (uintptr_t)blob_f16 | (uintptr_t)res_f32 | (uintptr_t)out_f32 |
-                  (uintptr_t)out_split_f16) & 15) == 0);
-  static bool attr = ((void)hipFuncSetAttribute((const void*)proj256_ln_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                LDS_BYTES), true);
-  (void)attr;
+  INK_CHECK_ARG(ink_aligned<16>(a_f32, blob_f16, res_f32, out_f32, out_split_f16));
+  ink_dyn_lds<proj256_ln_kernel>(LDS_BYTES);
   const int64_t ntiles = (rows + BM - 1) / BM;
   INK_CHECK_ARG(ntiles < (int64_t)1 << 31);
   hipLaunchKernelGGL(proj256_ln_kernel, dim3((unsigned)ntiles), dim3(256), LDS_BYTES, (hipStream_t)stream, a_f32,

@@ -166,7 +166,7 @@ extern "C" int ink_mask_cleanup(const void* masks_u8, int32_t n, int32_t H, int3
   const int Wp = (W + 63) / 64;
   INK_CHECK_ARG((int64_t)Wp * 8 <= (int64_t)W);
   u64* planes = (u64*)a;
-  INK_CHECK_ARG(((uintptr_t)planes & 7) == 0);
+  INK_CHECK_ARG(ink_aligned<8>(planes));
   hipLaunchKernelGGL(bp_pack_kernel, dim3((H * Wp + 3) / 4, n), dim3(256), 0, s, (const uint8_t*)b, H, W, Wp, 0, planes);
   if (hipMemsetAsync(workspace, 0, sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   return cc_run(planes, (int64_t)H * Wp, n, H, W, Wp, cleanup_rm(W, k), 1, area_threshold, aspect_threshold,

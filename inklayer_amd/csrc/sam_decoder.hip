@@ -187,17 +187,13 @@ __global__ __launch_bounds__(256) void mask_embed_kernel(const float* __restrict
     const int64_t row = (int64_t)p * g * g + tok;
     *(f32x4*)(keys + row * ME + 4 * c4) = v;
     if (split) {
-      f16x4 hi, lo, hs;
+      f16 hi[4], lo[4], hs[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (f16)v[e];
-        lo[e] = (f16)((v[e] - (float)hi[e]) * 64.0f);
-        hs[e] = (f16)((float)hi[e] * 0.015625f);
-      }
+      for (int e = 0; e < 4; ++e) split_f16(v[e], hi[e], lo[e], hs[e]);
       f16* sp = split + row * 3 * ME + 4 * c4;
-      *(f16x4*)sp = hi;
-      *(f16x4*)(sp + ME) = lo;
-      *(f16x4*)(sp + 2 * ME) = hs;
+      *(f16x4*)sp = (f16x4){hi[0], hi[1], hi[2], hi[3]};
+      *(f16x4*)(sp + ME) = (f16x4){lo[0], lo[1], lo[2], lo[3]};
+      *(f16x4*)(sp + 2 * ME) = (f16x4){hs[0], hs[1], hs[2], hs[3]};
     }
   }
 }
@@ -341,8 +337,8 @@ extern "C" int ink_sam_postprocess(const float* low, int32_t n, int32_t S, int32
   INK_CHECK_ARG(low && (out_u8 || out_logits) && n > 0 && S > 0 && L >= S);
   INK_CHECK_ARG(in_h > 0 && in_w > 0 && in_h <= L && in_w <= L && out_h > 0 && out_w > 0);
   const int64_t total = (int64_t)n * out_h * out_w;
-  if (out_w % 4 == 0 && (int64_t)n * out_h < (int64_t)1 << 30 && ((uintptr_t)out_u8 & 3) == 0 &&
-      ((uintptr_t)out_logits & 15) == 0) {
+  if (out_w % 4 == 0 && (int64_t)n * out_h < (int64_t)1 << 30 && ink_aligned<4>(out_u8) &&
+      ink_aligned<16>(out_logits)) {
     const int64_t rows = (int64_t)n * out_h;
     const int blocks = (int)(rows < 8192 ? rows : 8192);
     hipLaunchKernelGGL(postprocess_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, low, n, S, L, in_h,
@@ -373,7 +369,7 @@ extern "C" int ink_sam_mask_embed(const float* mask, const float* emb, const int
                                   int32_t n_params, float eps, int32_t P, int32_t g, float* keys, void* split_f16,
                                   void* stream) {
   INK_CHECK_ARG(mask && emb && emb_rows && params && keys && P > 0 && g > 0 && g <= 64 && n_params == MP_TOTAL);
-  INK_CHECK_ARG((((uintptr_t)mask | (uintptr_t)emb | (uintptr_t)keys) & 15) == 0 && ((uintptr_t)split_f16 & 7) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(mask, emb, keys) && ink_aligned<8>(split_f16));
   hipLaunchKernelGGL(mask_embed_kernel, dim3((unsigned)(P * g)), dim3(256), 0, (hipStream_t)stream, mask, emb, emb_rows,
                      params, eps, g, keys, (f16*)split_f16);
   return ink_launch_status();

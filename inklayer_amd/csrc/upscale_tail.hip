@@ -16,7 +16,7 @@
 // per lane and tile against 48 MFMAs.  Everything up to the second GELU is shared by the M masks, only the dot
 // products and the stores repeat; the dot of every mask runs in the same order, so mask m of a 4-mask launch equals a
 // single-mask launch with hyper vector m bit for bit.
-#include "common.h"
+#include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
 
 namespace {
@@ -26,10 +26,6 @@ constexpr int KS = 3 * CI / 16;                // 12 k-steps of the split operan
 constexpr int BLK = 1024;
 constexpr int W_BYTES = (CO / 32) * KS * BLK;  // 48 KiB
 constexpr int LDS_BYTES = W_BYTES + CO * 4 + 2 * CI * 4;
-
-__device__ __forceinline__ f32x16 mfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 // ws f16 [128, 192] (ops.split_weight layout) -> blob: block (jt, s) = 64 lanes x 8 halves, lane (l, hh) holds
 // ws[32 jt + l][16 s + 8 hh .. + 8]
@@ -94,10 +90,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float v = gelu_erf((x[2 * s + h2][e] - mean) * rstd * gm[e] + bt[e]);
-          const f16 hi = (f16)v;
+          f16 hi, lo, hs;
+          split_f16(v, hi, lo, hs);
           bf[s][4 * h2 + e] = hi;
-          bf[4 + s][4 * h2 + e] = (f16)((v - (float)hi) * 64.0f);
-          bf[8 + s][4 * h2 + e] = (f16)((float)hi * 0.015625f);
+          bf[4 + s][4 * h2 + e] = lo;
+          bf[8 + s][4 * h2 + e] = hs;
         }
       }
     // ---- [64 -> 4 x 32] projection: D^T[j, m], tile jt = sub-pixel s2; accumulators start from the bias
@@ -152,9 +149,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int M>
 int launch_tail(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const float* ln_g, const float* ln_b, float eps,
                 const f16* blob, const float* b3, const float* hyper, float* low, hipStream_t stream) {
-  static bool attr = ((void)hipFuncSetAttribute((const void*)upscale_tail_kernel<M>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), true);
-  (void)attr;
+  ink_dyn_lds<upscale_tail_kernel<M>>(LDS_BYTES);
   const int64_t n_tiles = (int64_t)n * g * g * 4 / 32;
   const int grid = (int)(n_tiles / 4 < 1024 ? (n_tiles + 3) / 4 : 1024);
   hipLaunchKernelGGL(upscale_tail_kernel<M>, dim3(grid), dim3(256), LDS_BYTES, stream, u0, ld_tok, n_tiles, ln_g, ln_b, eps,
@@ -165,7 +160,7 @@ int launch_tail(const float* u0, int64_t ld_tok, int32_t n, int32_t g, const flo
 }  // namespace
 
 extern "C" int ink_sam_upscale_pack(const void* ws_f16, void* blob_f16, void* stream) {
-  INK_CHECK_ARG(ws_f16 && blob_f16 && ((((uintptr_t)ws_f16 | (uintptr_t)blob_f16) & 15) == 0));
+  INK_CHECK_ARG(ws_f16 && blob_f16 && ink_aligned<16>(ws_f16, blob_f16));
   hipLaunchKernelGGL(upscale_pack_kernel, dim3(((CO / 32) * KS * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const f16*)ws_f16, (f16*)blob_f16);
   return ink_launch_status();
@@ -177,7 +172,7 @@ extern "C" int ink_sam_upscale_tail(const float* u0, int64_t ld_tok, int32_t n, 
   INK_CHECK_ARG(n_masks == 1 || n_masks == 3 || n_masks == 4);
   INK_CHECK_ARG(u0 && ln_g && ln_b && blob_f16 && b3 && hyper && low && n > 0 && g > 0 && (g * g * 4) % 32 == 0);
   INK_CHECK_ARG(ld_tok >= 4 * CI && ld_tok % 4 == 0);
-  INK_CHECK_ARG((((uintptr_t)u0 | (uintptr_t)blob_f16 | (uintptr_t)hyper | (uintptr_t)low) & 15) == 0);
+  INK_CHECK_ARG(ink_aligned<16>(u0, blob_f16, hyper, low));
   const auto launch = n_masks == 1 ? launch_tail<1> : n_masks == 3 ? launch_tail<3> : launch_tail<4>;
   return launch(u0, ld_tok, n, g, ln_g, ln_b, eps, (const f16*)blob_f16, b3, hyper, low, (hipStream_t)stream);
 }

@@ -159,7 +159,6 @@ __global__ __launch_bounds__(256) void vis_colour_kernel(const uint8_t* __restri
   }
 }
 
-static inline bool vis_al4(const void* q) { return ((uintptr_t)q & 3u) == 0; }
 static inline bool vis_dims_ok(int channels, int H, int W) {
   return (channels == 1 || channels == 3) && H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 40);
 }
@@ -173,7 +172,7 @@ extern "C" int ink_vis_gray_min(const void* sketch_u8, int32_t channels, int32_t
   const int64_t npix = (int64_t)H * W;
   if (hipMemsetAsync(gray_min, 0x7f, sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   hipLaunchKernelGGL(vis_gray_min_kernel, dim3((unsigned)((npix + 4095) / 4096)), dim3(256), 0, s,
-                     (const uint8_t*)sketch_u8, channels, npix, vis_al4(sketch_u8) ? VIS_AL_SKETCH : 0, gray_min);
+                     (const uint8_t*)sketch_u8, channels, npix, ink_aligned<4>(sketch_u8) ? VIS_AL_SKETCH : 0, gray_min);
   return ink_launch_status();
 }
 
@@ -183,8 +182,8 @@ extern "C" int ink_vis_colour(const void* sketch_u8, int32_t channels, const voi
   INK_CHECK_ARG(sketch_u8 && tables_u8 && gray_min && out_rgb_u8 && vis_dims_ok(channels, H, W) && n >= 0);
   INK_CHECK_ARG(by_label ? (masks_or_label_u8 && n <= 255) : (masks_or_label_u8 || n == 0));
   const int64_t npix = (int64_t)H * W;
-  int aligned = (vis_al4(sketch_u8) ? VIS_AL_SKETCH : 0) | (vis_al4(out_rgb_u8) ? VIS_AL_OUT : 0);
-  if (vis_al4(masks_or_label_u8) && (by_label || (npix & 3) == 0)) aligned |= VIS_AL_MASKS;
+  int aligned = (ink_aligned<4>(sketch_u8) ? VIS_AL_SKETCH : 0) | (ink_aligned<4>(out_rgb_u8) ? VIS_AL_OUT : 0);
+  if (ink_aligned<4>(masks_or_label_u8) && (by_label || (npix & 3) == 0)) aligned |= VIS_AL_MASKS;
   hipLaunchKernelGGL(vis_colour_kernel, dim3((unsigned)((npix + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream,
                      (const uint8_t*)sketch_u8, channels, (const uint8_t*)masks_or_label_u8, n, by_label ? 1 : 0,
                      (const uint8_t*)tables_u8, gray_min, npix, aligned, (uint8_t*)out_rgb_u8);

@@ -133,6 +133,76 @@ def test_refine_stage_argument_contract():
     assert ws(7, 129, ctypes.byref(pw), ctypes.byref(ci)) == 0 and pw.value == 4 * 7 * 3 and ci.value > 7 * 7 * 65
 
 
+def _misaligned_cases():
+    """name -> (well-formed arguments with fake pointers, {pointer argument: the alignment its entry point demands})
+    for the entry points whose pointer checks go through ink_aligned (csrc/common.h) and that no other test module
+    feeds a misaligned pointer.  Not here because the check cannot fail a call before a launch: ink_mask_cleanup
+    (refine.hip: the pointer is derived from the workspace after the first passes), and the alignment tests of
+    msda.hip, visualize.hip, ink_sam_postprocess and ink_eval_*'s vector paths, which choose a kernel, not an error
+    (tests/test_visualize_gpu.py, tests/test_evaluate_gpu.py feed those misaligned buffers)."""
+    p = 4096
+    return {
+        "ink_proj256_ln_pack": (dict(ws=p, blob=p), dict(ws=16, blob=16)),
+        "ink_proj256_ln": (dict(a=p, blob=p, bias=p, res=p, rbr=None, rpb=0, g=p, b=p, eps=1e-6, rows=128, out=p, split=p),
+                           dict(a=16, blob=16, res=16, out=16, split=16)),
+        "ink_ffn256_pack": (dict(w1=p, b1=p, w2=p, hid=2048, wpre=p, blob=p), dict(w1=16, wpre=16, blob=16)),
+        "ink_ffn256_fused": (dict(x=p, ldx=256, res=p, blob=p, b2=p, g=p, b=p, eps=1e-5, M=128, hid=2048, pb=p, pg=p,
+                                  pbe=p, out=p),
+                             dict(x=16, res=16, blob=16, b2=16, g=16, b=16, pb=16, pg=16, pbe=16, out=16)),
+        "ink_sam_upscale_pack": (dict(ws=p, blob=p), dict(ws=16, blob=16)),
+        "ink_sam_upscale_tail": (dict(u0=p, ld=512, n=1, g=64, lg=p, lb=p, eps=1e-6, blob=p, b3=p, hyper=p, M=3, low=p),
+                                 dict(u0=16, blob=16, hyper=16, low=16)),
+        "ink_conv3x3_f16": (dict(x=p, B=1, H=4, W=4, C=64, w=p, N=8, bias=p, stride=1, relu_in=0, act=0, res=p, out=p,
+                                 f16=0),
+                            dict(x=16, w=16, bias=16, res=16, out=16)),
+        "ink_sam_mask_embed": (dict(mask=p, emb=p, rows=p, prm=p, n_prm=4684, eps=1e-6, P=1, g=64, keys=p, split=p),
+                               dict(mask=16, emb=16, keys=16, split=8)),
+        "ink_relpos_bias64_f16": (dict(Q=p, ldq=3840, rh=p, rw=p, nb=1, nh=1, hd=80, scale=0.1, oh=p, ow=p),
+                                  dict(oh=16, ow=16)),
+        "ink_sam_amg_stats": (dict(low=p, n=1, index=None, m=1, m_dev=None, S=256, L=1024, in_h=768, in_w=1024,
+                                   crop_h=600, crop_w=800, thr=0.0, off=1.0, x0=0, y0=0, oh=600, ow=800, table=p,
+                                   planes=p, logits=p),
+                              dict(planes=8, logits=16)),           # crop_w % 4 == 0: the row kernel's 16-byte logits
+        "ink_mask_rle_counts": (dict(planes=p, sel=None, k=1, H=600, W=800, n=p), dict(planes=8)),
+        "ink_mask_rle_write": (dict(planes=p, sel=None, k=1, H=600, W=800, offs=p, counts=p), dict(planes=8)),
+        "ink_box_nms": (dict(boxes=p, scores=p, n=4, iou=0.7, ws=p, keep=p, n_keep=p), dict(ws=16)),
+        "ink_mask_small_regions": (dict(planes=p, k=1, H=600, W=800, area=100, holes=1, tmp=p, ws=p, out=p, changed=p),
+                                   dict(planes=8, tmp=8, ws=8, out=8)),
+        "ink_eval_label_ranks": (dict(lab=p, es=1, H=8, W=8, ws=p, vals=p, cap=256, info=p, rank=p), dict(rank=2)),
+        "ink_eval_contingency": (dict(pred=p, n=2, by_label=0, rank=p, U=3, sk=p, ch=3, so=1, H=8, W=8, T=p),
+                                 dict(rank=2)),
+        "ink_eval_label_boxes": (dict(rank=p, U=3, H=8, W=8, boxes=p), dict(rank=2)),
+        "ink_eval_paint_labels": (dict(rank=p, col=p, U=3, H=8, W=8, out=p), dict(rank=2)),
+    }
+
+
+def test_misaligned_pointers_are_refused_without_launch():
+    """Every pointer that an entry point's alignment check names, offset by HALF the demanded alignment while every
+    other argument is valid, makes the call return 1 before any HIP call.  Fake non-null pointers: none of these calls
+    may be accepted.  (Looked up by name from a table, as in test_refine_stage_argument_contract.)"""
+    from inklayer_amd import _lib
+    l = _lib.lib()
+    for name, (args, ptrs) in _misaligned_cases().items():
+        fn = getattr(l, name)
+        for arg, align in ptrs.items():
+            assert args[arg] % align == 0 and align >= 2
+            assert fn(*{**args, arg: args[arg] + align // 2}.values(), None) == 1, (name, arg)
+    # ink_flash_attn takes a struct: q, k, v rows in 16-byte, o rows in 8-byte pieces; the window form's pad rows
+    def attn(**kw):
+        a = _lib.InkAttn()
+        a.Q = a.K = a.V = a.O = 4096
+        a.ldq = a.ldk = a.ldv = 3 * 96 + 8
+        a.ldo = 96
+        a.n_batch, a.n_heads, a.n_q, a.n_k, a.head_dim, a.scale = 2, 3, 49, 49, 32, 0.25
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return l.ink_flash_attn(ctypes.byref(a), None)
+    assert attn(Q=4104) == 1 and attn(K=4104) == 1 and attn(V=4104) == 1 and attn(O=4100) == 1
+    win = dict(head_dim=80, bias_mode=2, rel_aug=4096, grid_w=14, n_q=196, n_k=196, ldq=3840, ldk=3840, ldv=3840,
+               ldo=1280, tok_rows=4096, pad_k=4096, pad_v=4096)
+    assert attn(**{**win, "pad_k": 4104}) == 1 and attn(**{**win, "pad_v": 4104}) == 1
+
+
 def test_attn_few_wrappers_refuse_misaligned_rows():
     """ops.attn_fewkeys / ops.attn_fewq assert 16-byte aligned q, k, v before anything native is called (CPU tensors: a
     view that starts 8 bytes into a row)."""
