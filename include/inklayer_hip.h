@@ -126,7 +126,11 @@ int ink_add_f32(const float* a, const float* b, int64_t n_b, float* out, int64_t
  *              [n_heads, n_q, 64] (relative_position_bias_table gathered by relative_position_index)
  *              + optional dense_mask f32 [n_mask, n_q, 64] (the 0/-100 SW-MSA mask; batch entry b
  *              uses mask b % n_mask).  Both are PRE-DIVIDED by `scale` and row-padded to 64.
- * Supported head_dim: 80 (modes 0,1,2), 32 (modes 0,3) and 16 (mode 0).
+ * Supported (head_dim, bias_mode) pairs: (80, 0), (80, 1), (80, 2), (64, 0), (64, 1), (64, 2), (32, 0), (32, 3),
+ * (16, 0); anything else returns INK_ERR_ARG.  head_dim 64 with modes 1 and 2 (SAM ViT-B / ViT-L) runs the generic
+ * templated kernel of csrc/attention.hip with the argument rules of head_dim 80 (mode 1: grid_w == 64,
+ * n_k % 64 == 0, n_k <= 4096; mode 2: grid_w <= 16, n_k <= grid_w^2) and f32 rel_h / rel_w only: rel_f16 != 0 is a
+ * head_dim-80 feature (csrc/attention_glob.hip) and returns INK_ERR_ARG at head_dim 64.
  * q_batch_rows / kv_batch_rows (int32 [n_batch], optional): first row of batch entry b in Q/O and
  * in K/V; NULL means b*n_q and b*n_k.  Lets many batch entries share one K/V (or Q) block, e.g.
  * SAM decoder layer 0 where the image keys are identical for all boxes of an image.
@@ -163,8 +167,9 @@ int ink_relpos_bias64_f16(const void* Q, int64_t ldq, const float* rel_pos_h, co
 /* Decomposed relative-position terms of SA/modeling/image_encoder.py:292-361
  * (get_rel_pos + the two einsums of add_decomposed_rel_pos), divided by `scale`:
  *   rel_h[bh, q, j] = (Q[b, q, h, :] . rel_pos_h[q_h - j + S - 1, :]) / scale   (same for w).
- * rel_pos_h / rel_pos_w: f32 [2S-1, head_dim].  S == 64 writes out_h/out_w (f32 [.., 64]);
- * S <= 16 writes out_aug_f16 ([.., 32], rel_h then rel_w then zeros).
+ * rel_pos_h / rel_pos_w: f32 [2S-1, head_dim], head_dim 80 (SAM ViT-H) or 64 (ViT-B / ViT-L) in both forms:
+ * S == 64 writes out_h/out_w (f32 [.., 64]); S == 14 writes out_aug_f16 ([.., 32], rel_h then rel_w then zeros).
+ * Any other head_dim returns INK_ERR_ARG (ink_relpos_bias64_f16 above stays head_dim 80 only).
  * tok_rows (optional, S <= 16 only): as in InkAttn - query i of window b is row tok_rows[b*S*S+i]
  * of Q (-1: padding, its output row is left untouched). */
 int ink_relpos_bias(const void* Q, int64_t ldq, const float* rel_pos_h, const float* rel_pos_w,

@@ -20,6 +20,8 @@
 //                   prefetch of the next block, and can gather/scatter token rows (tok_rows) so that SAM's
 //                   window partition / padding never materialises.
 // Streamed K/V (all other instances): 64-key tiles alternate between two LDS buffers, one barrier per tile.
+// Modes 1 and 2 exist at head_dim 80 (SAM ViT-H; its own shapes go to attention_glob.hip / attention_win.hip) and at
+// head_dim 64 (SAM ViT-B / ViT-L: these instances are the product path; row sum on the VALU, see LSUM_MFMA).
 #include <stdlib.h>
 #include "mfma_util.h"
 #include "../../include/inklayer_hip.h"
@@ -641,6 +643,18 @@ extern "C" int ink_flash_attn(const InkAttn* pp, void* stream) {
         (p.tok_rows || (int64_t)p.n_batch * p.n_q * p.ldo * 2 < 0x80000000LL))
       return ink_win4_attn_launch(p, n_cus, s);
     INK_FA_X(80, 2, 7, true);
+  } else if (p.head_dim == 64 && p.bias_mode == 1) {
+    // SAM ViT-B / ViT-L global blocks: the streamed kernel with f32 tables.  V's padded width equals the head width
+    // here (no ones-column), so the row sum is accumulated on the VALU
+    INK_CHECK_ARG(p.rel_h && p.rel_w && p.grid_w == 64 && p.n_k % 64 == 0 && p.n_k <= 64 * 64);
+    INK_CHECK_ARG(!p.rel_f16);          // f16 tables: head_dim 80 only (attention_glob.hip)
+    INK_FA(64, 1, 8);
+  } else if (p.head_dim == 64 && p.bias_mode == 2) {
+    // SAM ViT-B / ViT-L windows: the persistent all-keys-resident kernel
+    INK_CHECK_ARG(p.rel_aug && p.grid_w > 0 && p.grid_w <= 16 && p.n_k <= p.grid_w * p.grid_w && p.n_k <= 256);
+    INK_CHECK_ARG(!p.tok_rows || (p.n_q == p.n_k && p.pad_k && p.pad_v &&
+                                  ink_aligned<16>(p.pad_k, p.pad_v)));
+    INK_FA_X(64, 2, 7, true);
   } else if (p.head_dim == 80 && p.bias_mode == 0) {
     INK_FA(80, 0, 4);
   } else if (p.head_dim == 64 && p.bias_mode == 0) {
@@ -675,7 +689,7 @@ extern "C" int ink_relpos_bias(const void* Q, int64_t ldq, const float* rel_pos_
                                const float* rel_pos_w, int32_t S, int32_t n_batch,
                                int32_t n_heads, int32_t head_dim, float scale, const int32_t* tok_rows,
                                float* out_h, float* out_w, void* out_aug_f16, void* stream) {
-  INK_CHECK_ARG(Q && rel_pos_h && rel_pos_w && head_dim == 80 && ldq % 8 == 0);
+  INK_CHECK_ARG(Q && rel_pos_h && rel_pos_w && (head_dim == 80 || head_dim == 64) && ldq % 8 == 0);
   INK_CHECK_ARG(n_batch > 0 && n_heads > 0 && S > 0 && scale > 0.f);
   if (out_aug_f16) {
     INK_CHECK_ARG(S <= 16);
@@ -687,10 +701,18 @@ extern "C" int ink_relpos_bias(const void* Q, int64_t ldq, const float* rel_pos_
   const int nbh = n_batch * n_heads;
   if (out_aug_f16) {
     INK_CHECK_ARG(S == 14);
-    hipLaunchKernelGGL((relpos_mfma_kernel<80, 14, true>), dim3(nbh), dim3(256), 0, st, q, ldq, rel_pos_h,
-                       rel_pos_w, n_heads, 1.0f / scale, tok_rows, out_h, out_w, (f16*)out_aug_f16);
-  } else {
+    if (head_dim == 80) {
+      hipLaunchKernelGGL((relpos_mfma_kernel<80, 14, true>), dim3(nbh), dim3(256), 0, st, q, ldq, rel_pos_h,
+                         rel_pos_w, n_heads, 1.0f / scale, tok_rows, out_h, out_w, (f16*)out_aug_f16);
+    } else {
+      hipLaunchKernelGGL((relpos_mfma_kernel<64, 14, true>), dim3(nbh), dim3(256), 0, st, q, ldq, rel_pos_h,
+                         rel_pos_w, n_heads, 1.0f / scale, tok_rows, out_h, out_w, (f16*)out_aug_f16);
+    }
+  } else if (head_dim == 80) {
     hipLaunchKernelGGL((relpos_mfma_kernel<80, 64, false>), dim3(nbh * 16), dim3(256), 0, st, q, ldq, rel_pos_h,
+                       rel_pos_w, n_heads, 1.0f / scale, (const int32_t*)nullptr, out_h, out_w, (f16*)nullptr);
+  } else {
+    hipLaunchKernelGGL((relpos_mfma_kernel<64, 64, false>), dim3(nbh * 16), dim3(256), 0, st, q, ldq, rel_pos_h,
                        rel_pos_w, n_heads, 1.0f / scale, (const int32_t*)nullptr, out_h, out_w, (f16*)nullptr);
   }
   return ink_launch_status();

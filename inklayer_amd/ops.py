@@ -297,8 +297,8 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: in
 def relpos_bias(q: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tensor, *, S: int,
                 n_batch: int, n_heads: int, head_dim: int, scale: float, out=None,
                 tok_rows: Optional[torch.Tensor] = None, f16_tables: bool = False):
-    """SAM decomposed rel-pos terms / scale.  S == 64 -> (rel_h, rel_w) f32 (f16 with f16_tables: SAM's own attention shape
-    only); S <= 16 -> rel_aug f16."""
+    """SAM decomposed rel-pos terms / scale, head_dim 80 (ViT-H) or 64 (ViT-B / ViT-L).  S == 64 -> (rel_h, rel_w) f32
+    (f16 with f16_tables: SAM's own attention shape at head_dim 80 only); S == 14 -> rel_aug f16."""
     assert q.dtype == F16 and q.stride(1) == 1
     assert rel_pos_h.dtype == F32 and rel_pos_h.is_contiguous()
     assert rel_pos_w.dtype == F32 and rel_pos_w.is_contiguous()

@@ -3,7 +3,9 @@
 Mirrors the reference surfaces for this path
   * segment_anything.build_sam / SamPredictor  (SA/build_sam.py:55-107, SA/predictor.py:17-243)
   * InkLayer.segmentor.sam.run_SAM              (InkLayer/segmentor/sam.py:16-43)
-with the same state_dict key names, so `sam_vit_h_4b8939.pth` drops in unchanged.
+with the same state_dict key names, so `sam_vit_h_4b8939.pth` drops in unchanged; so do `sam_vit_l_0b3195.pth` and
+`sam_vit_b_01ec64.pth` (SAM_CONFIGS / sam_model_registry: the encoder's shape is read off the checkpoint; head width 64
+runs the templated attention of csrc/attention.hip with f32 rel-pos tables, ViT-H its dedicated kernels).
 
 Design (MI355X-first, not a translation of the nn.Module tree):
   * tokens live as ONE f32 residual stream [B*4096, 1280]; every GEMM input is produced in
@@ -24,7 +26,7 @@ No torch compute ops are used on the hot path — torch supplies memory, streams
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -59,6 +61,71 @@ class SamConfig:
     @property
     def grid(self) -> int:
         return self.img_size // self.patch_size
+
+    @property
+    def head_dim(self) -> int:
+        return self.embed_dim // self.num_heads
+
+
+# The three encoders of sam_model_registry (SA/build_sam.py:14-52); prompt encoder and mask decoder are the same for all.
+SAM_CONFIGS: Dict[str, SamConfig] = {
+    "vit_h": SamConfig(embed_dim=1280, depth=32, num_heads=16, global_attn_indexes=(7, 15, 23, 31)),
+    "vit_l": SamConfig(embed_dim=1024, depth=24, num_heads=16, global_attn_indexes=(5, 11, 17, 23)),
+    "vit_b": SamConfig(embed_dim=768, depth=12, num_heads=12, global_attn_indexes=(2, 5, 8, 11)),
+}
+HEAD_DIMS = (64, 80)     # head widths the rel-pos attention kernels serve (csrc/attention*.hip)
+
+
+def config_for(name: str) -> SamConfig:
+    """The registry entry of `name` (a copy); "default" is ViT-H as in the reference.  ValueError for an unknown name."""
+    key = "vit_h" if name == "default" else name
+    if key not in SAM_CONFIGS:
+        raise ValueError(f"unknown SAM model {name!r}: one of {sorted(SAM_CONFIGS)}")
+    return replace(SAM_CONFIGS[key])
+
+
+def model_name(cfg: SamConfig) -> Optional[str]:
+    """The registry name of a configuration, None when it is none of the three."""
+    return next((n for n, c in SAM_CONFIGS.items() if c == cfg), None)
+
+
+def config_from_state_dict(sd) -> SamConfig:
+    """The encoder a SAM state dict holds, from its tensor shapes alone (values: tensors on any device, "meta"
+    included, or shape tuples): embed dim and grid from image_encoder.pos_embed, depth from the block count, head dim
+    from blocks.0.attn.rel_pos_h, the global blocks are those whose rel_pos_h has 2 * grid - 1 rows, window size from a
+    windowed block's table, patch size from patch_embed.proj.weight, mlp_ratio from blocks.0.mlp.lin1.weight.
+    ValueError, naming what was found, when that is not a model the kernels serve: head dim in {64, 80}, a 64 x 64 grid,
+    14 x 14 windows."""
+    def shape(k):
+        if k not in sd:
+            raise ValueError(f"not a SAM state dict: {k} is missing")
+        v = sd[k]
+        return tuple(int(d) for d in (v.shape if hasattr(v, "shape") else v))
+
+    pre = "image_encoder.blocks."
+    pos = shape("image_encoder.pos_embed")
+    if len(pos) != 4 or pos[0] != 1 or pos[1] != pos[2]:
+        raise ValueError(f"not a SAM state dict: image_encoder.pos_embed has shape {pos}")
+    g, D = pos[1], pos[3]
+    blocks = {int(k[len(pre):].split(".", 1)[0]) for k in sd if k.startswith(pre)}
+    depth = len(blocks)
+    if depth == 0 or blocks != set(range(depth)):
+        raise ValueError(f"not a SAM state dict: image encoder blocks {sorted(blocks)}")
+    rows = [shape(f"{pre}{i}.attn.rel_pos_h") for i in range(depth)]
+    hd = rows[0][1]
+    glob = tuple(i for i, r in enumerate(rows) if r[0] == 2 * g - 1)
+    wins = sorted({(r[0] + 1) // 2 for i, r in enumerate(rows) if i not in glob})
+    patch = shape("image_encoder.patch_embed.proj.weight")[-1]
+    hidden = shape(f"{pre}0.mlp.lin1.weight")[0]
+    found = (f"embed dim {D}, {depth} blocks, head dim {hd}, a {g} x {g} grid, global blocks {glob}, "
+             f"window sizes {wins}, patch size {patch}")
+    if any(r[1] != hd for r in rows) or hd <= 0 or D % hd or len(wins) > 1:
+        raise ValueError(f"inconsistent SAM image encoder: {found}")
+    if hd not in HEAD_DIMS or g != 64 or (wins and wins[0] != 14):
+        raise ValueError(f"no kernels for this SAM image encoder ({found}): the attention kernels serve head dim "
+                         f"{' or '.join(map(str, HEAD_DIMS))}, a 64 x 64 grid and 14 x 14 windows")
+    return SamConfig(embed_dim=D, depth=depth, num_heads=D // hd, global_attn_indexes=glob,
+                     window_size=wins[0] if wins else 14, img_size=g * patch, patch_size=patch, mlp_ratio=hidden / D)
 
 
 def preprocess_shape(h: int, w: int, L: int) -> Tuple[int, int]:
@@ -200,14 +267,14 @@ class SamEngine:
         self.cfg, self.dev = cfg, torch.device(device)
         assert self.dev.type == "cuda", "the InkLayer segmentor runs on MI355X only"
         D, g = cfg.embed_dim, cfg.grid
-        assert D // cfg.num_heads == 80 and g == 64 and cfg.window_size == 14, \
-            "HIP attention kernels are specialised for SAM's head_dim 80 / 64x64 grid / 14x14 windows"
+        assert D % cfg.num_heads == 0 and cfg.head_dim in HEAD_DIMS and g == 64 and cfg.window_size == 14, \
+            "HIP attention kernels are specialised for SAM's head_dim 80 or 64 / 64x64 grid / 14x14 windows"
         E = cfg.prompt_embed_dim
         assert E // cfg.dec_heads == 32 and (E // 2) // cfg.dec_heads == 16
         self.T = g * g
         assert E == 256 and (self.T * 4) % 32 == 0, \
             "the fused decoder kernels (csrc/proj_ln.hip, csrc/upscale_tail.hip) are built for SAM's widths"
-        self.scale = 80 ** -0.5
+        self.scale = cfg.head_dim ** -0.5
         sd = state_dict
         dev = self.dev
 
@@ -386,9 +453,11 @@ class SamEngine:
         H = cfg.num_heads
         self.rel_aug = e(B * nwin * nwin * H * ws * ws, 32)
         # decomposed rel-pos terms of the global blocks as f16 tables (the one-wave-per-SIMD kernel converts them on the
-        # way into LDS / the exponent: half the bytes written by relpos_bias and read back)
-        self.rel_h = e(B * H * T, 64)
-        self.rel_w = e(B * H * T, 64)
+        # way into LDS / the exponent: half the bytes written by relpos_bias and read back).  That kernel is head_dim 80
+        # only: at head_dim 64 (ViT-B / ViT-L) the templated kernel of attention.hip reads f32 tables
+        self.rel_f16 = cfg.head_dim == 80
+        self.rel_h = e(B * H * T, 64, dt=F16 if self.rel_f16 else F32)
+        self.rel_w = e(B * H * T, 64, dt=F16 if self.rel_f16 else F32)
 
     # ------------------------------------------------------------------ encoder
     def encode(self, images_u8: Sequence[torch.Tensor], chan_reverse: bool = False,
@@ -462,9 +531,9 @@ class SamEngine:
             q, kk, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
             if i in cfg.global_attn_indexes:
                 rh, rw = ops.relpos_bias(q, w[k + "attn.rel_pos_h"], w[k + "attn.rel_pos_w"], S=cfg.grid,
-                                         n_batch=B, n_heads=H, head_dim=80, scale=self.scale,
-                                         out=(self.rel_h, self.rel_w), f16_tables=True)
-                o = ops.flash_attn(q, kk, v, n_batch=B, n_heads=H, head_dim=80, scale=self.scale,
+                                         n_batch=B, n_heads=H, head_dim=cfg.head_dim, scale=self.scale,
+                                         out=(self.rel_h, self.rel_w), f16_tables=self.rel_f16)
+                o = ops.flash_attn(q, kk, v, n_batch=B, n_heads=H, head_dim=cfg.head_dim, scale=self.scale,
                                    rel_h=rh, rel_w=rw, grid_w=cfg.grid, out=self.att[:B * T])
             else:
                 # windowed block: everything stays in token order; window_partition / window_unpartition
@@ -473,9 +542,9 @@ class SamEngine:
                 wm = self.win_map[:B * Mw]
                 nb = B * self.nwin * self.nwin
                 aug = ops.relpos_bias(q, w[k + "attn.rel_pos_h"], w[k + "attn.rel_pos_w"],
-                                      S=cfg.window_size, n_batch=nb, n_heads=H, head_dim=80,
+                                      S=cfg.window_size, n_batch=nb, n_heads=H, head_dim=cfg.head_dim,
                                       scale=self.scale, out=self.rel_aug, tok_rows=wm)
-                o = ops.flash_attn(q, kk, v, n_batch=nb, n_heads=H, head_dim=80, scale=self.scale,
+                o = ops.flash_attn(q, kk, v, n_batch=nb, n_heads=H, head_dim=cfg.head_dim, scale=self.scale,
                                    n_q=cfg.window_size ** 2, n_k=cfg.window_size ** 2,
                                    rel_aug=aug, grid_w=cfg.window_size, tok_rows=wm,
                                    pad_k=w[k + "pad_k"], pad_v=w[k + "pad_v"], out=self.att[:B * T])
@@ -750,19 +819,51 @@ class SamPredictor:
 _ENGINES: Dict[str, SamEngine] = {}
 
 
+def _check_model_type(cfg: SamConfig, model_type: Optional[str], source: str) -> None:
+    if model_type is not None and config_for(model_type) != cfg:
+        held = model_name(cfg) or f"{cfg.embed_dim}-wide, {cfg.depth}-block"
+        raise ValueError(f"{source} holds a SAM {held} model, not the {model_type!r} asked for")
+
+
 def build_sam(checkpoint: Optional[str] = None, state_dict=None, device="cuda",
-              max_batch: int = 1) -> SamEngine:
-    """SA/build_sam.py:55-107 (ViT-H).  Unlike the reference (which rebuilds the model and reloads
+              max_batch: int = 1, model_type: Optional[str] = None) -> SamEngine:
+    """SA/build_sam.py:55-107 for ViT-H, ViT-L and ViT-B: the encoder's shape is read off the state dict
+    (config_from_state_dict), so any of the three checkpoints loads unchanged; model_type, if given, must name what the
+    state dict holds (ValueError otherwise).  Unlike the reference (which rebuilds the model and reloads
     the 2.4 GB checkpoint on EVERY run_SAM call, InkLayer/segmentor/sam.py:23) the engine is cached
     per checkpoint path and stays resident in HBM."""
+    source = str(checkpoint) if state_dict is None else "the state dict"
     if state_dict is None:
         if checkpoint in _ENGINES:
+            _check_model_type(_ENGINES[checkpoint].cfg, model_type, source)
             return _ENGINES[checkpoint]
         state_dict = torch.load(checkpoint, map_location="cpu", weights_only=True)
-    eng = SamEngine(state_dict, SamConfig(), device, max_batch)
+    cfg = config_from_state_dict(state_dict)
+    _check_model_type(cfg, model_type, source)
+    eng = SamEngine(state_dict, cfg, device, max_batch)
     if checkpoint is not None:
         _ENGINES[checkpoint] = eng
     return eng
+
+
+def _registry_builder(model_type: str):
+    def builder(checkpoint: Optional[str] = None, device="cuda", max_batch: int = 1) -> SamEngine:
+        """sam_model_registry[...](checkpoint=...) of SA/build_sam.py:14-52, returning an engine.  Without a checkpoint the
+        reference returns the untrained model; here that is an engine on seeded random weights."""
+        if checkpoint is None:
+            from . import weights_init
+            cfg = config_for(model_type)
+            return SamEngine(weights_init.random_sam_state_dict(cfg, device), cfg, device, max_batch)
+        return build_sam(checkpoint, device=device, max_batch=max_batch, model_type=model_type)
+    builder.__name__ = builder.__qualname__ = f"build_sam_{model_type}"
+    return builder
+
+
+build_sam_vit_h = _registry_builder("vit_h")
+build_sam_vit_l = _registry_builder("vit_l")
+build_sam_vit_b = _registry_builder("vit_b")
+sam_model_registry = {"default": build_sam_vit_h, "vit_h": build_sam_vit_h, "vit_l": build_sam_vit_l,
+                      "vit_b": build_sam_vit_b}
 
 
 def run_SAM(image_pil, boxes_filt: torch.Tensor, sam_checkpoint: Optional[str] = None,
