@@ -131,9 +131,11 @@ int ink_add_f32(const float* a, const float* b, int64_t n_b, float* out, int64_t
  * templated kernel of csrc/attention.hip with the argument rules of head_dim 80 (mode 1: grid_w == 64,
  * n_k % 64 == 0, n_k <= 4096; mode 2: grid_w <= 16, n_k <= grid_w^2) and f32 rel_h / rel_w only: rel_f16 != 0 is a
  * head_dim-80 feature (csrc/attention_glob.hip) and returns INK_ERR_ARG at head_dim 64.
- * q_batch_rows / kv_batch_rows (int32 [n_batch], optional): first row of batch entry b in Q/O and
- * in K/V; NULL means b*n_q and b*n_k.  Lets many batch entries share one K/V (or Q) block, e.g.
- * SAM decoder layer 0 where the image keys are identical for all boxes of an image.
+ * q_batch_rows / kv_batch_rows (int32 [n_batch], optional): first row of batch entry b in Q and in K/V;
+ * NULL means b*n_q and b*n_k.  Lets many batch entries share one K/V (or Q) block, e.g.
+ * SAM decoder layer 0 where the image keys are identical for all boxes of an image.  The tables redirect reads
+ * only.  O is always dense: row b*n_q + i holds query i of entry b (entries that share Q rows still get their
+ * own output rows), unless tok_rows scatters it.
  * tok_rows (int32 [n_batch, n_q], optional, bias_mode 2 only, n_q == n_k): token i of batch entry
  *   (window) b lives in row tok_rows[b*n_q + i] of Q, K, V AND O, or is window padding (-1).  This
  *   is window_partition / window_unpartition (SA/modeling/image_encoder.py:243-289) folded into

@@ -79,19 +79,21 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
   struct QState { bool ok; int64_t row; };
   // ALLKV + tok_rows: the token rows of a window depend on the window only, not on the head, and a workgroup walks
   // consecutive heads of the same window, so they are cached in registers (wrow_q, wrow_k) and re-read only when
-  // the window changes - the prefetch of the next block then has no dependent load in it
+  // the window changes - the prefetch of the next block then has no dependent load in it.  The query rows also
+  // depend on the query block (n_q = 256 has two): the cache is keyed on (window, query block)
   constexpr int KALL = ALLKV ? (MAXT * 64 * CH + NT - 1) / NT : 1;
   int wrow_q = 0, wrow_k[KALL], wrow_b = -1;
-  auto load_wrows = [&](int b_) {
-    if (MODE == 2 && ALLKV && p.tok_rows && b_ != wrow_b) {
-      const int qi = wave * 32 + lq;
+  auto load_wrows = [&](int blk_) {
+    const int b_ = (blk_ / nqb) / p.n_heads, qb_ = blk_ % nqb;
+    if (MODE == 2 && ALLKV && p.tok_rows && b_ * nqb + qb_ != wrow_b) {
+      const int qi = qb_ * NW * 32 + wave * 32 + lq;
       wrow_q = p.tok_rows[(int64_t)b_ * p.n_q + (qi < p.n_q ? qi : p.n_q - 1)];
 #pragma unroll
       for (int it = 0; it < KALL; ++it) {
         const int key = (tid + it * NT) / CH;
         wrow_k[it] = key < p.n_k ? p.tok_rows[(int64_t)b_ * p.n_k + key] : -1;
       }
-      wrow_b = b_;
+      wrow_b = b_ * nqb + qb_;
     }
   };
   auto load_q = [&](int blk_, f16x8 (&dst)[NQK]) -> QState {
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
       }
     }
   };
-  load_wrows((blk / nqb) / p.n_heads);
+  load_wrows(blk);
   f16x8 qf[NQK];
   QState qs = load_q(blk, qf);
   if constexpr (ALLKV) load_kv_all(blk);
@@ -299,7 +301,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_kernel(InkAttn p) {
     }
     __syncthreads();
     if (blk + 1 < blk_end) {
-      load_wrows(((blk + 1) / nqb) / p.n_heads);   // a (rare) window change costs one exposed round trip
+      load_wrows(blk + 1);                         // a (rare) window change costs one exposed round trip
       load_kv_all(blk + 1);
     }
   } else {
@@ -628,7 +630,7 @@ extern "C" int ink_flash_attn(const InkAttn* pp, void* stream) {
   }
 #define INK_FA(HD, MODE, NW) INK_FA_X(HD, MODE, NW, false)
   if (p.head_dim == 80 && p.bias_mode == 1) {
-    INK_CHECK_ARG(p.rel_h && p.rel_w && p.grid_w == 64 && p.n_k % 64 == 0);
+    INK_CHECK_ARG(p.rel_h && p.rel_w && p.grid_w == 64 && p.n_k % 64 == 0 && p.n_k <= 64 * 64);   // rel_h has 64 key rows
     // SAM's own shape (64 x 64 tokens): the one-wave-per-SIMD kernel of attention_glob.hip
     if (p.n_q % 256 == 0 && p.n_k % 128 == 0 && p.n_k >= 256 && p.n_k <= 4096) return ink_glob4_attn_launch(p, s);
     INK_CHECK_ARG(!p.rel_f16);          // f16 tables: the one-wave-per-SIMD kernel only
