@@ -162,6 +162,26 @@ typedef struct InkAttn {
 } InkAttn;
 int ink_flash_attn(const InkAttn* p, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Swin window attention with the relative-position bias and the SW-MSA mask computed in the kernel (ABI 9 gained
+ * this one entry point; nothing else changed, so the version stays 9).  Per window w and head h
+ *   O = softmax(scale q k^T + bias_table[h][rel(q, k)] + (region[w % nW][q] != region[w % nW][k] ? -100 : 0)) v
+ * with rel(q, k) = (qy - ky + ws - 1) * (2 ws - 1) + (qx - kx + ws - 1), token i of a window at (i / ws, i % ws):
+ * WindowAttention.forward (GD/.../swin_transformer.py:134-174) with relative_position_index (:111-121) and the
+ * attn_mask of BasicLayer.forward (:417-441).  It serves the windows bias_mode 3 of ink_flash_attn cannot (ws = 12:
+ * 144 tokens, Swin-B/384) without dense per-window tables; ws = 7 is served too, so the two can be compared.
+ * Token i of window w is row w * ws^2 + i of Q, K, V (f16; head h in columns [32 h, 32 h + 32); column slices of the
+ * packed qkv buffer: only the row strides matter) and of the dense output O f16 [n_windows * ws^2, >= n_heads * 32].
+ * bias_table: f32 [n_heads, (2 ws - 1)^2], LOGIT units (relative_position_bias_table transposed; not divided by scale).
+ * region: uint8 [nW, ws^2] ids (the nine-slice labelling of the shifted image), or NULL for an unshifted block.
+ * head_dim is 32.  Refused with INK_ERR_ARG before any launch: ws other than 7 or 12; a null Q / K / V / O /
+ * bias_table; a row stride that is not a multiple of 8 or is below n_heads * 32; Q / K / V not 16-byte or O not 8-byte
+ * aligned; region with nW <= 0; nW > 0 with n_windows % nW != 0; n_windows, n_heads or scale <= 0.
+ * --------------------------------------------------------------------- */
+int ink_swin_attn(const void* Q, const void* K, const void* V, int64_t ldq, int64_t ldk, int64_t ldv,
+                  void* O, int64_t ldo, int32_t n_windows, int32_t n_heads, int32_t ws, float scale,
+                  const float* bias_table, const uint8_t* region, int32_t nW, void* stream);
+
 /* ink_relpos_bias for the 64 x 64 grid with f16 output tables [n_batch*n_heads*4096, 64] (InkAttn.rel_f16 = 1). */
 int ink_relpos_bias64_f16(const void* Q, int64_t ldq, const float* rel_pos_h, const float* rel_pos_w, int32_t n_batch,
                           int32_t n_heads, int32_t head_dim, float scale, void* out_h_f16, void* out_w_f16, void* stream);

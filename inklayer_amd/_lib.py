@@ -50,6 +50,8 @@ SIGNATURES = {
     "ink_add_cvt_f16": [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p],
     "ink_add_f32": [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p],
     "ink_flash_attn": [C.POINTER(InkAttn), c_void_p],
+    "ink_swin_attn": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_float,
+                      c_void_p, c_void_p, c_int, c_void_p],
     "ink_sam_patchify": [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float),
                          c_int, c_int, c_void_p, c_void_p],
     "ink_im2col3x3_f16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],

@@ -41,9 +41,10 @@ def _newest_header() -> float:
 # fully unrolled register arrays; scratch there would mean one of them was indexed at run time.  evaluate.hip: the same
 # four-pixel arrays (membership words, ranks) in per-pixel counting kernels of a few dozen registers.  gemm.hip: the
 # accumulators of a tile and, in the direct 3x3 convolution, the per-chunk centre pointers and tap masks live across
-# the whole K loop; scratch there would put private-memory traffic into the MFMA loop.
+# the whole K loop; scratch there would put private-memory traffic into the MFMA loop.  attention_swin.hip: all scores
+# of a query (five accumulator tiles) and the next unit's prefetched rows live in registers; scratch would undo both.
 NO_SPILL = {"ffn_fused.hip", "proj_ln.hip", "amg.hip", "layers.hip", "inpaint_ops.hip", "visualize.hip", "evaluate.hip",
-            "gemm.hip"}
+            "gemm.hip", "attention_swin.hip"}
 
 
 def _check_no_spill(src: Path, remarks: str) -> None:

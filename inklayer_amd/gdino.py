@@ -1,4 +1,4 @@
-"""GroundingDINO Swin-T box proposer on MI355X: host-side composition of the HIP kernels.
+"""GroundingDINO (Swin-T / Swin-B) box proposer on MI355X: host-side composition of the HIP kernels.
 
 Mirrors groundingdino.util.inference.{load_image, predict} and GroundingDINO.forward
 (GD/util/inference.py:39-97, GD/models/GroundingDINO/groundingdino.py:227-365) with the reference's
@@ -21,7 +21,7 @@ Equal-sized images per batch (NestedTensor masks all False) — what InkLayer fe
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -35,7 +35,7 @@ F16, F32, I32 = torch.float16, torch.float32, torch.int32
 
 @dataclass
 class GDinoConfig:
-    """models/GroundingDINO_SwinT_OGC.py:1-43 + swin_T_224_1k."""
+    """models/GroundingDINO_SwinT_OGC.py:1-43 + swin_T_224_1k (the default); the Swin-B backbones: GDINO_CONFIGS."""
     embed_dim: int = 96
     depths: Tuple[int, ...] = (2, 2, 6, 2)
     num_heads: Tuple[int, ...] = (3, 6, 12, 24)
@@ -54,6 +54,104 @@ class GDinoConfig:
     box_threshold: float = 0.2
     pixel_mean: Tuple[float, ...] = (0.485, 0.456, 0.406)
     pixel_std: Tuple[float, ...] = (0.229, 0.224, 0.225)
+
+
+# The backbones of build_swin_transformer (GD/models/GroundingDINO/backbone/swin_transformer.py:757-795) that the two
+# public GroundingDINO configs name (GroundingDINO_SwinT_OGC.py, GroundingDINO_SwinB_cfg.py), keyed as there; the
+# transformer on top is the same for all of them.
+GDINO_CONFIGS: Dict[str, GDinoConfig] = {
+    "swin_T_224_1k": GDinoConfig(),
+    "swin_B_224_22k": GDinoConfig(embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window_size=7),
+    "swin_B_384_22k": GDinoConfig(embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window_size=12),
+}
+GDINO_ALIASES = {"swin_t": "swin_T_224_1k", "swin_b": "swin_B_384_22k"}
+WINDOW_SIZES = (7, 12)   # 7: ink_flash_attn bias_mode 3 (dense tables); 12: ink_swin_attn (csrc/attention_swin.hip)
+HEAD_DIM = 32            # the head width both Swin attention kernels are built for
+
+
+def config_for(name: str) -> GDinoConfig:
+    """The registry entry of `name` (a copy): a backbone name of the reference or one of the aliases swin_t / swin_b.
+    ValueError for an unknown name."""
+    key = GDINO_ALIASES.get(name, name)
+    if key not in GDINO_CONFIGS:
+        raise ValueError(f"unknown GroundingDINO model {name!r}: one of {sorted(GDINO_CONFIGS) + sorted(GDINO_ALIASES)}")
+    return replace(GDINO_CONFIGS[key])
+
+
+def model_name(cfg: GDinoConfig) -> Optional[str]:
+    """The reference's backbone name of a configuration's Swin shapes, None when it is none of the registry's."""
+    key = (cfg.embed_dim, tuple(cfg.depths), tuple(cfg.num_heads), cfg.window_size)
+    return next((n for n, c in GDINO_CONFIGS.items()
+                 if (c.embed_dim, tuple(c.depths), tuple(c.num_heads), c.window_size) == key), None)
+
+
+def check_config(cfg: GDinoConfig) -> None:
+    """ValueError, naming what was found, unless the kernels serve `cfg`: Swin heads of width 32, a window size with an
+    attention kernel, and the transformer shapes the fused detector kernels are built for.  No device is touched."""
+    widths = [cfg.embed_dim * 2 ** i / nh for i, nh in enumerate(cfg.num_heads)]
+    if len(cfg.depths) != len(cfg.num_heads) or any(wd != HEAD_DIM for wd in widths):
+        raise ValueError(f"no kernels for this Swin backbone: head widths {widths} (embed dim {cfg.embed_dim}, heads "
+                         f"{tuple(cfg.num_heads)}, depths {tuple(cfg.depths)}); the window attention kernels serve head "
+                         f"width {HEAD_DIM}")
+    if cfg.window_size not in WINDOW_SIZES:
+        raise ValueError(f"no kernels for this Swin backbone: window size {cfg.window_size}; the window attention "
+                         f"kernels serve {' and '.join(map(str, WINDOW_SIZES))}")
+    if cfg.embed_dim * 2 ** (len(cfg.depths) - 1) > 2048:
+        raise ValueError(f"no kernels for this Swin backbone: {cfg.embed_dim * 2 ** (len(cfg.depths) - 1)} channels in "
+                         f"the last stage; the row LayerNorm serves at most 2048 (and the patch merging half of that)")
+    if (cfg.hidden_dim, cfg.nheads, cfg.num_feature_levels, cfg.n_points) != (256, 8, 4, 4):
+        raise ValueError(f"no kernels for this detector transformer: hidden_dim {cfg.hidden_dim}, nheads {cfg.nheads}, "
+                         f"num_feature_levels {cfg.num_feature_levels}, n_points {cfg.n_points}; the kernels serve "
+                         f"hidden_dim 256, 8 heads, 4 levels, 4 points")
+
+
+def config_from_state_dict(sd) -> GDinoConfig:
+    """The model a GroundingDINO state dict holds, from its tensor shapes alone (values: tensors on any device, "meta"
+    included, or shape tuples; a DataParallel "module." prefix is stripped): embed_dim from patch_embed.proj.weight,
+    depths by counting each stage's blocks, heads and window size from each stage's relative_position_bias_table
+    ((2 ws - 1)^2, nh), out_indices from the backbone.0.norm{i} present, hidden_dim and levels from level_embed, layers
+    by counting, queries from tgt_embed, dim_feedforward from linear1.  ValueError, naming what was found, when that is
+    not a model the kernels serve (check_config) - before anything is allocated."""
+    sd = clean_state_dict(sd)
+
+    def shape(k):
+        if k not in sd:
+            raise ValueError(f"not a GroundingDINO state dict: {k} is missing")
+        v = sd[k]
+        return tuple(int(d) for d in (v.shape if hasattr(v, "shape") else v))
+
+    def count(prefix):
+        ids = {int(k[len(prefix):].split(".", 1)[0]) for k in sd if k.startswith(prefix)}
+        if ids != set(range(len(ids))):
+            raise ValueError(f"not a GroundingDINO state dict: {prefix}* holds indices {sorted(ids)}")
+        return len(ids)
+
+    bb, t = "backbone.0.", "transformer."
+    C0 = shape(bb + "patch_embed.proj.weight")[0]
+    depths = tuple(count(f"{bb}layers.{i}.blocks.") for i in range(count(bb + "layers.")))
+    if not depths or 0 in depths:
+        raise ValueError(f"not a GroundingDINO state dict: Swin stage depths {depths}")
+    tabs = [[shape(f"{bb}layers.{i}.blocks.{b}.attn.relative_position_bias_table") for b in range(d)]
+            for i, d in enumerate(depths)]
+    flat = [tb for st in tabs for tb in st]
+    sides = sorted({math.isqrt(tb[0]) for tb in flat})
+    heads = tuple(st[0][1] for st in tabs)
+    if (any(len(tb) != 2 for tb in flat) or any(tb[1] != st[0][1] for st in tabs for tb in st) or len(sides) != 1
+            or sides[0] ** 2 != flat[0][0] or sides[0] % 2 == 0):
+        raise ValueError(f"inconsistent Swin backbone: relative_position_bias_table shapes {sorted(set(flat))}")
+    ws = (sides[0] + 1) // 2
+    out_indices = tuple(i for i in range(len(depths)) if f"{bb}norm{i}.weight" in sd)
+    lv = shape(t + "level_embed")
+    so = shape(t + "encoder.layers.0.self_attn.sampling_offsets.weight")
+    cfg = GDinoConfig(embed_dim=C0, depths=depths, num_heads=heads, window_size=ws, out_indices=out_indices,
+                      hidden_dim=lv[1], num_feature_levels=lv[0], enc_layers=count(t + "encoder.layers."),
+                      dec_layers=count(t + "decoder.layers."), num_queries=shape(t + "tgt_embed.weight")[0],
+                      dim_feedforward=shape(t + "encoder.layers.0.linear1.weight")[0])
+    check_config(cfg)
+    if so != (cfg.nheads * lv[0] * cfg.n_points * 2, lv[1]):
+        raise ValueError(f"no kernels for this detector transformer: sampling_offsets.weight has shape {so}, not "
+                         f"{(cfg.nheads * lv[0] * cfg.n_points * 2, lv[1])} (8 heads x 4 levels x 4 points x 2)")
+    return cfg
 
 
 # caption "object." -> [CLS] object . [SEP]; ids of bert-base-uncased ("object" = 4874 cannot be
@@ -119,9 +217,10 @@ class _Plan:
         self.stage_hw: List[Tuple[int, int]] = []
         self.win_map: List[List[torch.Tensor]] = []      # [stage][shifted] int32 [B*nW*49]
         self.nW: List[int] = []
-        self.shift_mask: List[torch.Tensor] = []         # [stage] f32 [nW, 49, 64], pre-divided by scale
+        self.shift_mask: List[torch.Tensor] = []         # [stage] f32 [nW, 49, 64], pre-divided by scale (ws == 7)
+        self.region: List[torch.Tensor] = []             # [stage] uint8 [nW, ws*ws] nine-slice ids (ws != 7)
         self.merge_map: List[Optional[torch.Tensor]] = []
-        scale = 32 ** -0.5
+        scale = HEAD_DIM ** -0.5
         for i in range(len(cfg.depths)):
             self.stage_hw.append((H, W))
             Hp, Wp = -(-H // ws) * ws, -(-W // ws) * ws
@@ -138,17 +237,14 @@ class _Plan:
                 maps.append(full.to(I32).to(dev))
             self.win_map.append(maps)
             # SW-MSA mask of BasicLayer.forward (swin_transformer.py:417-441)
-            img = torch.zeros((Hp, Wp))
-            cnt = 0
-            for hs in (slice(0, -ws), slice(-ws, -sh), slice(-sh, None)):
-                for wsl in (slice(0, -ws), slice(-ws, -sh), slice(-sh, None)):
-                    img[hs, wsl] = cnt
-                    cnt += 1
-            mw = img.view(Hp // ws, ws, Wp // ws, ws).permute(0, 2, 1, 3).reshape(nW, ws * ws)
-            diff = mw[:, None, :] - mw[:, :, None]
-            m = torch.zeros((nW, ws * ws, 64))
-            m[:, :, :ws * ws] = torch.where(diff != 0, torch.tensor(-100.0), torch.tensor(0.0)) / scale
-            self.shift_mask.append(m.to(dev).contiguous())
+            mw = swin_regions(Hp, Wp, ws)
+            if ws == 7:
+                diff = mw[:, None, :] - mw[:, :, None]
+                m = torch.zeros((nW, ws * ws, 64))
+                m[:, :, :ws * ws] = torch.where(diff != 0, torch.tensor(-100.0), torch.tensor(0.0)) / scale
+                self.shift_mask.append(m.to(dev).contiguous())
+            else:                                # ops.swin_attn compares the ids itself: no [nW, ws^2, ws^2] table
+                self.region.append(mw.to(torch.uint8).to(dev).contiguous())
             if i < len(cfg.depths) - 1:
                 H2, W2 = (H + 1) // 2, (W + 1) // 2
                 y2, x2 = torch.meshgrid(torch.arange(H2), torch.arange(W2), indexing="ij")
@@ -205,6 +301,19 @@ class _Plan:
         self.valid_map = torch.where(valid, torch.arange(self.S), torch.full((self.S,), -1)).to(I32).to(dev)
 
 
+def swin_regions(Hp: int, Wp: int, ws: int) -> torch.Tensor:
+    """The nine-slice labelling of the padded, shifted image of BasicLayer.forward (swin_transformer.py:417-432) in
+    window order: f32 [nW, ws*ws] ids 0..8.  Two tokens of a window attend to each other iff their ids are equal."""
+    sh = ws // 2
+    img = torch.zeros((Hp, Wp))
+    cnt = 0
+    for hs in (slice(0, -ws), slice(-ws, -sh), slice(-sh, None)):
+        for wsl in (slice(0, -ws), slice(-ws, -sh), slice(-sh, None)):
+            img[hs, wsl] = cnt
+            cnt += 1
+    return img.view(Hp // ws, ws, Wp // ws, ws).permute(0, 2, 1, 3).reshape(-1, ws * ws)
+
+
 def swin_dense_bias(table: torch.Tensor, ws: int, nh: int, scale: float) -> torch.Tensor:
     """The relative-position bias of one Swin block (swin_transformer.py:111-121, 159-163) as flash_attn's dense_bias:
     f32 [nh, ws*ws, 64], query rows x key columns, pre-divided by the softmax scale, columns ws*ws.. zero."""
@@ -217,6 +326,14 @@ def swin_dense_bias(table: torch.Tensor, ws: int, nh: int, scale: float) -> torc
     bias = torch.zeros((nh, ws * ws, 64))
     bias[:, :, :ws * ws] = table[rel_index].view(ws * ws, ws * ws, nh).permute(2, 0, 1) / scale
     return bias
+
+
+def swin_bias_table(table: torch.Tensor, ws: int, nh: int) -> torch.Tensor:
+    """The relative-position bias table of one Swin block as ops.swin_attn takes it: f32 [nh, (2 ws - 1)^2], logit
+    units, contiguous; the kernel indexes it with (qy - ky + ws - 1) (2 ws - 1) + (qx - kx + ws - 1), which is
+    relative_position_index (swin_transformer.py:111-121)."""
+    assert tuple(table.shape) == ((2 * ws - 1) ** 2, nh)
+    return table.to(torch.float32).t().contiguous()
 
 
 def clean_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -238,8 +355,7 @@ class GDinoEngine:
         cfg = cfg or GDinoConfig()
         self.cfg, self.dev = cfg, torch.device(device)
         assert self.dev.type == "cuda", "the InkLayer detector runs on MI355X only"
-        assert cfg.hidden_dim == 256 and cfg.nheads == 8 and cfg.num_feature_levels == 4 and cfg.n_points == 4
-        assert all(cfg.embed_dim * 2 ** i // nh == 32 for i, nh in enumerate(cfg.num_heads))
+        check_config(cfg)
         sd, dev = clean_state_dict(state_dict), self.dev
         self.w: Dict[str, torch.Tensor] = {}
         w = self.w
@@ -268,7 +384,7 @@ class GDinoEngine:
         w["pe.b"] = f(bb + "patch_embed.proj.bias")
         ln("pe.norm", bb + "patch_embed.norm")
         ws = cfg.window_size
-        scale = 32 ** -0.5
+        scale = HEAD_DIM ** -0.5
         for i, (dep, nh) in enumerate(zip(cfg.depths, cfg.num_heads)):
             for b in range(dep):
                 p, d = f"{bb}layers.{i}.blocks.{b}.", f"s{i}b{b}"
@@ -279,7 +395,10 @@ class GDinoEngine:
                 lin(d + ".fc1", p + "mlp.fc1")
                 lin(d + ".fc2", p + "mlp.fc2")
                 tab = sd[p + "attn.relative_position_bias_table"].detach().to(torch.float32).cpu()
-                w[d + ".bias"] = swin_dense_bias(tab, ws, nh, scale).to(dev).contiguous()
+                if ws == 7:
+                    w[d + ".bias"] = swin_dense_bias(tab, ws, nh, scale).to(dev).contiguous()
+                else:
+                    w[d + ".table"] = swin_bias_table(tab, ws, nh).to(dev).contiguous()
             if i < len(cfg.depths) - 1:
                 ln(f"s{i}.merge.norm", f"{bb}layers.{i}.downsample.norm")
                 w[f"s{i}.merge.w"] = h(f"{bb}layers.{i}.downsample.reduction.weight")
@@ -435,9 +554,14 @@ class GDinoEngine:
         wm = pl.win_map[i][1 if shifted else 0]
         y = ops.layernorm_rows(x, w[d + ".norm1.w"], w[d + ".norm1.b"], 1e-5, gather=wm)
         qkv = ops.gemm(y, w[d + ".qkv.w"], w[d + ".qkv.b"], out_dtype=F16)
-        o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_batch=pl.B * nW, n_heads=nh,
-                           head_dim=32, scale=32 ** -0.5, n_q=49, n_k=49, dense_bias=w[d + ".bias"],
-                           dense_mask=pl.shift_mask[i] if shifted else None)
+        ws, scale = cfg.window_size, HEAD_DIM ** -0.5
+        if ws == 7:
+            o = ops.flash_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_batch=pl.B * nW, n_heads=nh,
+                               head_dim=HEAD_DIM, scale=scale, n_q=ws * ws, n_k=ws * ws, dense_bias=w[d + ".bias"],
+                               dense_mask=pl.shift_mask[i] if shifted else None)
+        else:
+            o = ops.swin_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_windows=pl.B * nW, n_heads=nh, ws=ws,
+                              scale=scale, bias_table=w[d + ".table"], region=pl.region[i] if shifted else None, nW=nW)
         ops.gemm(o, w[d + ".proj.w"], w[d + ".proj.b"], residual=x, row_map=wm, out=x)
         y = ops.layernorm_rows(x, w[d + ".norm2.w"], w[d + ".norm2.b"], 1e-5)
         hmid = ops.gemm(y, w[d + ".fc1.w"], w[d + ".fc1.b"], act="gelu", out_dtype=F16)

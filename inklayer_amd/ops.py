@@ -294,6 +294,38 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: in
     return out
 
 
+SWIN_ATTN_WINDOWS = (7, 12)        # the window sizes csrc/attention_swin.hip serves
+
+
+def swin_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_windows: int, n_heads: int, ws: int, scale: float,
+              bias_table: torch.Tensor, region: Optional[torch.Tensor] = None, nW: int = 0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Swin window attention, head_dim 32, bias and SW-MSA mask computed in the kernel (csrc/attention_swin.hip):
+    softmax(scale*q@k^T + bias_table[h][rel(q, k)] + (-100 where region[w % nW] differs))@v per (window, head).
+
+    q/k/v: f16 row views [n_windows*ws*ws, >= n_heads*32] (column slices of one packed qkv buffer: only the row stride
+    matters), token i of window w in row w*ws*ws + i.  bias_table f32 [n_heads, (2*ws-1)**2] in logit units; region
+    uint8 [nW, ws*ws] ids or None (unshifted block).  The output is dense f16 [n_windows*ws*ws, n_heads*32]."""
+    assert ws in SWIN_ATTN_WINDOWS, f"swin_attn serves window sizes {SWIN_ATTN_WINDOWS}, not {ws}"
+    rows = n_windows * ws * ws
+    for t in (q, k, v):
+        assert t.dtype == F16 and t.dim() == 2 and t.stride(1) == 1 and t.is_cuda
+        assert t.shape[0] >= rows and t.shape[1] >= n_heads * 32 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
+    assert bias_table.dtype == F32 and bias_table.is_contiguous() and bias_table.is_cuda
+    assert bias_table.shape == (n_heads, (2 * ws - 1) ** 2)
+    if region is not None:
+        assert region.dtype == torch.uint8 and region.is_contiguous() and region.is_cuda
+        assert nW > 0 and region.shape == (nW, ws * ws) and n_windows % nW == 0
+    if out is None:
+        out = torch.empty((rows, n_heads * 32), device=q.device, dtype=F16)
+    assert out.dtype == F16 and out.is_cuda and out.shape == (rows, n_heads * 32) and out.stride(1) == 1
+    assert out.stride(0) % 8 == 0 and out.data_ptr() % 8 == 0
+    check(_lib.lib().ink_swin_attn(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                   out.data_ptr(), out.stride(0), n_windows, n_heads, ws, scale, bias_table.data_ptr(),
+                                   _p(region), nW if region is not None else 0, _stream()), "ink_swin_attn")
+    return out
+
+
 def relpos_bias(q: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tensor, *, S: int,
                 n_batch: int, n_heads: int, head_dim: int, scale: float, out=None,
                 tok_rows: Optional[torch.Tensor] = None, f16_tables: bool = False):
