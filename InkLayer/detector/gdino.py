@@ -3,7 +3,11 @@
 `run_ft_dino_on_sketch(path) -> {"bboxes": normalised xyxy lists, "scores": [...], "labels": [...]}`
 with caption "object", box_threshold 0.2, text_threshold 0 exactly as the reference.  The model is a
 module-level singleton like the reference's `model`, but created on first use and kept resident in
-HBM (the reference re-`.to(device)`s it every call, GD/util/inference.py:64)."""
+HBM (the reference re-`.to(device)`s it every call, GD/util/inference.py:64).
+
+`predict(model, image, caption, box_threshold, text_threshold)` is the reference's open-vocabulary call
+(GD/util/inference.py:54-97): any caption of up to 256 tokens, a phrase per box.  `run_gdino_on_sketch` wraps it in
+run_ft_dino_on_sketch's dict shape with the real labels."""
 import os
 import re
 
@@ -63,7 +67,10 @@ def load_model(config_path=None, checkpoint_path=None, device="cuda"):
                              f"{cfg.depths}, heads {cfg.num_heads}, window {cfg.window_size}): use the config that "
                              f"belongs to the checkpoint")
         text = text_branch.encode_caption_from_checkpoint(sd, gdino.DEFAULT_TOKEN_IDS)
-    return gdino.GDinoEngine(sd, cfg, device, encoded_text=text)
+    eng = gdino.GDinoEngine(sd, cfg, device, encoded_text=text)
+    if os.environ.get("INKLAYER_RANDOM_WEIGHTS") != "1":      # later captions fold BERT from the same checkpoint
+        eng.text_weights = {k: v for k, v in sd.items() if k.startswith(("bert.", "feat_map."))}
+    return eng
 
 
 def get_model():
@@ -84,3 +91,68 @@ def run_ft_dino_on_sketch(sketch_path):
     boxes, scores = eng.detect([ops.resize_bilinear_u8(raw, oh, ow)])[0]
     normalized = cxcywh_to_xyxy(boxes.tolist()).tolist()        # cxcywh -> xyxy in float64
     return {"bboxes": normalized, "scores": scores.tolist(), "labels": ["object"] * len(normalized)}
+
+
+_tokenizer = None
+
+
+def get_tokenizer():
+    """The BERT-uncased WordPiece tokenizer over models/bert-base-uncased/vocab.txt or $INKLAYER_BERT_VOCAB
+    (FileNotFoundError without one: captions are then given as token ids)."""
+    global _tokenizer
+    if _tokenizer is None:
+        from inklayer_amd.wordpiece import WordPiece
+        _tokenizer = WordPiece()
+    return _tokenizer
+
+
+def _caption_ids(caption):
+    """(token ids, tokenizer or None) of a caption given as text (needs the vocabulary) or as a sequence of ids."""
+    if isinstance(caption, str):
+        tok = get_tokenizer()
+        return tok.encode(caption), tok
+    try:
+        tok = get_tokenizer()
+    except FileNotFoundError:
+        tok = None
+    return [int(t) for t in caption], tok
+
+
+def predict(model, image, caption, box_threshold, text_threshold, device="cuda", remove_combined=False):
+    """groundingdino.util.inference.predict (GD/util/inference.py:54-97) on the HIP engine `model` (load_model):
+    image an HWC uint8 RGB array or a path (resized as load_image does, on the GPU), caption a str - tokenized with the
+    BERT vocabulary - or a sequence of token ids ([CLS] ... [SEP]).  -> (boxes [n, 4] cxcywh normalised, scores [n],
+    phrases): phrases are strings where a vocabulary is available and id tuples otherwise.  `device` is accepted for the
+    reference's signature; the engine stays where it was loaded.  A caller that keeps one caption over many images sets
+    it once with model.set_caption and calls model.predict, which also keeps the captured HIP graphs."""
+    import torch
+    from inklayer_amd import gdino, ops
+    ids, tok = _caption_ids(caption)
+    if isinstance(image, (str, os.PathLike)):
+        image = np.asarray(Image.open(image).convert("RGB"))
+    raw = torch.from_numpy(np.ascontiguousarray(image)).to(model.dev)
+    oh, ow = gdino.resize_shape(image.shape[1], image.shape[0])
+    # like the reference's, this call is stateless in the caption: the engine (the singleton run_ft_dino_on_sketch
+    # shares) leaves with the caption and tokenizer it came with; its features wait in the engine's caption cache
+    held_ids, held_tok = tuple(model.token_ids), model.tokenizer
+    try:
+        if tuple(ids[:model.cfg.max_text_len]) != held_ids:
+            text = None
+            if os.environ.get("INKLAYER_RANDOM_WEIGHTS") == "1":  # no BERT weights either: stand-in features, as load_model
+                from inklayer_amd import weights_init
+                text = weights_init.random_text_features(model.cfg, "cpu", n_tokens=min(len(ids), model.cfg.max_text_len))
+            model.set_caption(ids, encoded_text=text)
+        model.tokenizer = tok
+        return model.predict([ops.resize_bilinear_u8(raw, oh, ow)], box_threshold, text_threshold, remove_combined)[0]
+    finally:
+        if tuple(model.token_ids) != held_ids:
+            model.set_caption(held_ids)
+        model.tokenizer = held_tok
+
+
+def run_gdino_on_sketch(sketch_path, caption, box_threshold=0.2, text_threshold=0.0):
+    """run_ft_dino_on_sketch's dict for any caption: {"bboxes": normalised xyxy lists, "scores", "labels": the phrase of
+    each box}."""
+    boxes, scores, phrases = predict(get_model(), sketch_path, caption, box_threshold, text_threshold)
+    normalized = cxcywh_to_xyxy(boxes.tolist()).tolist()
+    return {"bboxes": normalized, "scores": scores.tolist(), "labels": list(phrases)}

@@ -383,6 +383,26 @@ int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
                      const uint8_t* blocked, const int32_t* q_batch_rows, const float* q_add, int32_t io_f32, void* O,
                      int64_t ldo, void* stream);
 
+/* ink_attn_fewkeys' contract for n_k <= 256 keys on f16 rows (head_dim 32 or 64, f32 math, blocked u8 [n_q, n_k] or
+ * NULL, the same alignment rules; no q_batch_rows / q_add): the text attentions of a caption of 17..256 tokens.  A
+ * VALU kernel with an online softmax over blocks of 8 keys (csrc/attn_few.hip) - about 0.24 GFLOP per image and decoder
+ * layer, not MFMA work.  A fully blocked row gives zeros, not NaN. */
+int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, int32_t B,
+                     int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale, const uint8_t* blocked,
+                     void* O, int64_t ldo, void* stream);
+
+/* ink_biattn_fusion's semantics for 1 <= T <= 256 text tokens on f16 MFMA (csrc/biattn_wide.hip): QV f16 [B*S, 2E],
+ * KL f16 [B*T, 2E], E = 1024, S <= 32768; out_v f16 [B*S, E], out_l f16 [B*T, E].  No score matrix in HBM: the text side is
+ * a split over chunks of 1024 image tokens that recomputes the score tile, merged by a fourth kernel; no atomics, the
+ * results of image b do not depend on B.  ws: f32 [ink_biattn_wide_workspace(B, S, T)] = with Tp = 32 ceil(T / 32):
+ * B*4*(128 Tp + ceil(S/128) Tp + ceil(S/1024) Tp 258) floats.  Returns 1 with nothing launched for a null pointer, T
+ * outside 1..256, E != 1024, S outside 1..32768, B outside 1..65535 (the image is a grid dimension; the workspace
+ * query refuses the same ranges) or a base that is not 16-byte aligned.  (One more entry point
+ * of ABI 9, like ink_swin_attn before it.) */
+int ink_biattn_wide_workspace(int32_t B, int32_t S, int32_t T, int64_t* out_floats);
+int ink_biattn_wide(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, int32_t E, float scale,
+                    float* ws, void* out_v_f16, void* out_l_f16, void* stream);
+
 /* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
  * image: 7..16 x 4096, SA/modeling/transformer.py:163-168) on f32 rows: head h at columns [h*hd,(h+1)*hd), head_dim
  * must be 16 and n_heads a multiple of 4; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].

@@ -93,6 +93,84 @@ __global__ __launch_bounds__(256) void attn_fewkeys_kernel(const T* __restrict__
   for (int i = 0; i < HD / 8; ++i) store8(op + 8 * i, acc + 8 * i);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same contract for up to 256 keys (ink_attn_midkeys: the text attentions of a caption of 17..256 tokens), f16
+// rows.  Plain VALU, not MFMA: the work is about 0.24 GFLOP per image and decoder layer.  One thread per (batch, query,
+// head) as above, but the scores do not fit a register array, so the softmax is the online form over blocks of 8
+// keys: 8 independent dot products, one rescale of the accumulator per block.  f32 math.  A fully blocked row (it
+// cannot occur in the detector: a token always sees itself) gives zeros, not NaN.
+template <int HD>
+__global__ __launch_bounds__(256) void attn_midkeys_kernel(const f16* __restrict__ Q, int64_t ldq,
+                                                           const f16* __restrict__ K, int64_t ldk,
+                                                           const f16* __restrict__ V, int64_t ldv, int B, int n_q,
+                                                           int n_k, int n_heads, float scale,
+                                                           const uint8_t* __restrict__ blocked, f16* __restrict__ O,
+                                                           int64_t ldo) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)B * n_q * n_heads) return;
+  const int h = (int)(gid % n_heads);
+  const int64_t bq = gid / n_heads;
+  const int b = (int)(bq / n_q), q = (int)(bq % n_q);
+  float qv[HD];
+  const f16* qp = Q + bq * ldq + h * HD;
+#pragma unroll
+  for (int i = 0; i < HD / 8; ++i) load8(qp + 8 * i, qv + 8 * i);
+  float acc[HD];
+#pragma unroll
+  for (int i = 0; i < HD; ++i) acc[i] = 0.f;
+  float m = -3.0e38f, l = 0.f;
+  for (int t0 = 0; t0 < n_k; t0 += 8) {
+    float sc[8];
+    float bm = -3.0e38f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int t = t0 + u;
+      float d = -3.0e38f;
+      if (t < n_k && !(blocked && blocked[q * n_k + t])) {
+        const f16* kp = K + ((int64_t)b * n_k + t) * ldk + h * HD;
+        d = 0.f;
+#pragma unroll
+        for (int i = 0; i < HD / 8; ++i) {
+          float kv[8];
+          load8(kp + 8 * i, kv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) d = fmaf(qv[8 * i + j], kv[j], d);
+        }
+        d *= scale;
+      }
+      sc[u] = d;
+      bm = fmaxf(bm, d);
+    }
+    if (bm <= -1.0e38f) continue;                           // the whole block is blocked or past n_k
+    const float mn = fmaxf(m, bm);
+    const float a = expf(m - mn);                           // first live block: exp(-3e38 - mn) = 0 on acc = 0
+    l *= a;
+#pragma unroll
+    for (int i = 0; i < HD; ++i) acc[i] *= a;
+    m = mn;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (sc[u] <= -1.0e38f) continue;
+      const float pw = expf(sc[u] - m);
+      l += pw;
+      const f16* vp = V + ((int64_t)b * n_k + t0 + u) * ldv + h * HD;
+#pragma unroll
+      for (int i = 0; i < HD / 8; ++i) {
+        float vv[8];
+        load8(vp + 8 * i, vv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[8 * i + j] = fmaf(pw, vv[j], acc[8 * i + j]);
+      }
+    }
+  }
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+  for (int i = 0; i < HD; ++i) acc[i] *= inv;
+  f16* op = O + bq * ldo + h * HD;
+#pragma unroll
+  for (int i = 0; i < HD / 8; ++i) store8(op + 8 * i, acc + 8 * i);
+}
+
 
 // head_dim 16, f32 rows (the SAM decoder's image->token attention: 4096 queries x 7 keys per box, 8 heads): FOUR lanes
 // per (query, head), 4 of the 16 dimensions each, so that every load and store instruction of a wave covers one
@@ -393,6 +471,24 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
   } else if (head_dim == 16) INK_FEWKEYS(16, float);
   else return INK_ERR_ARG;
 #undef INK_FEWKEYS
+  return ink_launch_status();
+}
+
+extern "C" int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                int64_t ldv, int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads,
+                                int32_t head_dim, float scale, const uint8_t* blocked, void* O, int64_t ldo,
+                                void* stream) {
+  INK_CHECK_ARG(Q && K && V && O && B > 0 && n_q > 0 && n_k > 0 && n_k <= 256 && n_heads > 0);
+  INK_CHECK_ARG(head_dim == 32 || head_dim == 64);
+  INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
+  INK_CHECK_ARG(ink_aligned<16>(Q, K, V, O));            // 16-byte vectors, as in ink_attn_fewkeys
+  const int64_t total = (int64_t)B * n_q * n_heads;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define INK_MIDKEYS(HD)                                                                                            \
+  hipLaunchKernelGGL(attn_midkeys_kernel<HD>, grid, block, 0, (hipStream_t)stream, (const f16*)Q, ldq,             \
+                     (const f16*)K, ldk, (const f16*)V, ldv, B, n_q, n_k, n_heads, scale, blocked, (f16*)O, ldo)
+  if (head_dim == 32) INK_MIDKEYS(32); else INK_MIDKEYS(64);
+#undef INK_MIDKEYS
   return ink_launch_status();
 }
 

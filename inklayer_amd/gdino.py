@@ -13,9 +13,11 @@ MI355X-first structure (not a translation of the nn.Module tree):
   * Swin attention: relative-position bias (+ SW-MSA mask) enters through the MFMA accumulator init;
   * deformable attention: softmax, sampling-location arithmetic and bilinear gather in one kernel on an
     f16 value map; the two small Linear layers feeding it are one [256 -> 384] GEMM;
-  * image<->text fusion never builds the 13294 x T score matrix per head beyond a [S,4,T] f32 strip;
+  * image<->text fusion never builds the 13294 x T score matrix per head beyond a [S,4,T] f32 strip (T <= 4; a
+    caption of 5..256 tokens runs the three products on MFMA with no score matrix at all, csrc/biattn_wide.hip);
   * everything that does not depend on the pixels (sine position embeddings, reference points,
-    anchors, masks, maps, the BERT text features of the fixed caption "object.") is folded at load.
+    anchors, masks, maps, the BERT text features of the caption - "object." by default) is folded at load, or once
+    per caption (set_caption; predict returns a phrase per box).
 Equal-sized images per batch (NestedTensor masks all False) — what InkLayer feeds.
 """
 from __future__ import annotations
@@ -200,6 +202,41 @@ def text_masks_and_position_ids(input_ids: Sequence[int], special: Sequence[int]
             pos[prev + 1: col + 1] = torch.arange(0, col - prev)
         prev = col
     return attn, pos
+
+
+SEPARATOR_TOKENS = (101, 102, 1012)      # [CLS], [SEP], "." : the phrase boundaries of predict(remove_combined=True)
+
+
+def phrase_token_ids(posmap: Sequence[bool], token_ids: Sequence[int], left_idx: int = 0, right_idx: int = 255) -> List[int]:
+    """get_phrases_from_posmap (GD/util/utils.py:599-610) up to the tokenizer's decode: the ids of the tokens whose
+    posmap entry is set, positions 0..left_idx and right_idx.. excluded."""
+    return [int(token_ids[i]) for i, on in enumerate(posmap) if on and left_idx < i < right_idx]
+
+
+def phrases_from_probs(probs: torch.Tensor, token_ids: Sequence[int], text_threshold: float,
+                       remove_combined: bool = False, tokenizer=None) -> list:
+    """The phrase of every kept box, as predict (GD/util/inference.py:80-95) forms it from the sigmoided logits
+    probs [n, T] of the caption token_ids: the tokens above text_threshold, and with remove_combined only those between
+    the two separators ([CLS] / [SEP] / ".") around the box's strongest token (the sep_idx bisect; a strongest token at
+    or before the first separator wraps to the last one, as the reference's index -1 does; one past the last separator -
+    a caption cut at 256 tokens - ends at T, where the reference raises IndexError).  With a tokenizer (anything with
+    decode(ids) -> str) a phrase is the decoded string without "."; without one it is the tuple of ids without the
+    id of "." (1012)."""
+    import bisect
+    T = len(token_ids)
+    sep_idx = [i for i, t in enumerate(token_ids) if t in SEPARATOR_TOKENS]
+    out = []
+    for row in probs:
+        posmap = (row > text_threshold).tolist()
+        left, right = 0, 255
+        if remove_combined:
+            at = bisect.bisect_left(sep_idx, int(row.argmax()))
+            right = sep_idx[at] if at < len(sep_idx) else T
+            left = sep_idx[at - 1]
+        ids = phrase_token_ids(posmap, token_ids, left, right)
+        out.append(tokenizer.decode(ids).replace(".", "") if tokenizer is not None
+                   else tuple(t for t in ids if t != 1012))
+    return out
 
 
 def _interleaved_sincos(v: torch.Tensor) -> torch.Tensor:
@@ -470,24 +507,96 @@ class GDinoEngine:
         self._graphs = LRU(self.graph_cache_size)
         self._plans = LRU(self.plan_cache_size)
         self._seen: Dict[Tuple[int, int, int], int] = {}
+        self._captions = LRU(self.caption_cache_size)          # tuple(ids) -> encoded_text on the host (set_caption)
+        self.text_weights: Optional[Dict[str, torch.Tensor]] = None   # the checkpoint's bert.* / feat_map.* (host)
         self.set_text(encoded_text, token_ids)
 
+    @classmethod
+    def text_state_only(cls, cfg: Optional[GDinoConfig] = None, device: str | torch.device = "cpu") -> "GDinoEngine":
+        """An engine with no weights: everything set_text / set_caption read and write, on `device` (the CPU by default).
+        For the host-side checks of caption handling; it cannot run a forward."""
+        eng = cls.__new__(cls)
+        eng.cfg, eng.dev, eng.w = cfg or GDinoConfig(), torch.device(device), {}
+        eng._graphs, eng._plans, eng._seen = LRU(cls.graph_cache_size), LRU(cls.plan_cache_size), {}
+        eng._captions, eng.text_weights = LRU(cls.caption_cache_size), None
+        return eng
+
     def set_text(self, encoded_text: Optional[torch.Tensor], token_ids: Sequence[int]) -> None:
-        """encoded_text = feat_map(BERT(caption)) [T, 256] (groundingdino.py:277-279), a load-time constant."""
+        """encoded_text = feat_map(BERT(caption)) [T, 256] (groundingdino.py:277-279), a constant of the caption.
+        T <= cfg.max_text_len (256); a longer id list is truncated to that first, as groundingdino.py:259-266 does (a
+        phrase the cut runs through is left without its closing separator, so its tokens see only themselves).  ONE
+        caption per engine state, shared by every image of a batch: per-image captions with padding masks are out of
+        scope.  Plans stay (they do not depend on the text); captured graphs are dropped."""
         if encoded_text is None:
             raise ValueError("encoded_text [T,256] is required: fold BERT + feat_map once at load "
                              "(inklayer_amd.text_branch) or pass precomputed features")
-        T = encoded_text.shape[0]
-        assert T == len(token_ids) and T <= 4, "fusion kernel is specialised for captions of <= 4 tokens"
+        assert encoded_text.shape[0] == len(token_ids), "one feature row per token id"
+        token_ids = list(token_ids)[:self.cfg.max_text_len]      # groundingdino.py:259-266
+        encoded_text = encoded_text[:self.cfg.max_text_len]
+        T = len(token_ids)
+        assert T >= 1
         self._graphs.clear()                           # captured forwards hold the old text tensors
         self._seen.clear()
         self.T = T
+        self.token_ids = tuple(int(t) for t in token_ids)
+        # dispatch on T alone: <= 4 tokens take the folded / VALU fusion kernels, more the MFMA one (csrc/biattn_wide.hip);
+        # the text attentions keep their scores in registers up to 16 keys (csrc/attn_few.hip)
+        self._biattn = ops.biattn_fusion if T <= 4 else ops.biattn_wide
+        self._text_attn = ops.attn_fewkeys if T <= 16 else ops.attn_midkeys
         self.text0 = encoded_text.detach().to(self.dev, F32).contiguous()
-        sm, pid = text_masks_and_position_ids(list(token_ids))
+        self._captions.put(self.token_ids, encoded_text.detach().to("cpu", F32))    # set_caption finds it again
+        # ContrastiveEmbed's GEMM writes N % 4 == 0 columns: T is padded with zero text rows whose bias is -inf
+        self.Tc, self.logit_bias = -(-T // 4) * 4, None
+        if self.Tc != T:
+            self.logit_bias = torch.zeros(self.Tc, dtype=F32)
+            self.logit_bias[T:] = float("-inf")
+            self.logit_bias = self.logit_bias.to(self.dev)
+        sm, pid = text_masks_and_position_ids(token_ids)
         self.text_blocked = (~sm).to(torch.uint8).to(self.dev).contiguous()
         dim_t = torch.arange(256, dtype=torch.float32)
         dim_t = 10000.0 ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / 256)
         self.pos_text = _interleaved_sincos(pid.float()[:, None] * (2 * math.pi) / dim_t).to(self.dev).contiguous()
+
+    caption_cache_size = 8
+    tokenizer = None         # anything with decode(ids) -> str (inklayer_amd.wordpiece.WordPiece): predict's phrases as text
+
+    def set_caption(self, token_ids: Sequence[int], sd: Optional[Dict[str, torch.Tensor]] = None,
+                    encoded_text: Optional[torch.Tensor] = None) -> None:
+        """Switch the engine to the caption with these token ids ([CLS] ... [SEP], at most cfg.max_text_len are kept).
+        Its text features are encoded_text [T, 256] where given, else feat_map(BERT(ids)) folded on the host from the
+        checkpoint's bert.* / feat_map.* tensors (text_branch.encode_caption_from_checkpoint; sd is remembered from
+        the first call that passes one) - once per caption: the last `caption_cache_size` captions are kept.  BERT
+        is host-side torch and not on the hot path.  One caption per engine state, see set_text."""
+        ids = tuple(int(t) for t in token_ids)[:self.cfg.max_text_len]
+        if sd is not None:
+            sd = clean_state_dict(sd)
+            self.text_weights = {k: v for k, v in sd.items() if k.startswith(("bert.", "feat_map."))}
+            self._captions.clear()                          # features folded from another checkpoint
+        if encoded_text is None:
+            encoded_text = self._captions.get(ids)
+        if encoded_text is None:
+            if not self.text_weights:
+                raise ValueError("set_caption needs encoded_text [T, 256] or a state dict with the checkpoint's bert.* "
+                                 "and feat_map.* tensors")
+            from .text_branch import encode_caption_from_checkpoint
+            encoded_text = encode_caption_from_checkpoint(self.text_weights, ids)
+        self.set_text(encoded_text[:len(ids)], ids)
+
+    def predict(self, images_u8: Sequence[torch.Tensor], box_threshold: float, text_threshold: float,
+                remove_combined: bool = False):
+        """predict (GD/util/inference.py:70-97) per image for the engine's caption: [(boxes [n, 4] cxcywh, scores [n],
+        phrases)] with the boxes whose best token probability exceeds box_threshold; phrases as phrases_from_probs
+        forms them (strings with self.tokenizer set, id tuples without)."""
+        logits, boxes = self.forward(images_u8)
+        both = torch.cat([logits, boxes], dim=-1).cpu()       # single D2H copy
+        T, res = self.T, []
+        for b in range(both.shape[0]):
+            prob = both[b, :, :T].contiguous().sigmoid()      # dense [nq, T], as the reference's `.cpu().sigmoid()[0]`
+            keep = prob.max(dim=1)[0] > box_threshold
+            kept = prob[keep]
+            phrases = phrases_from_probs(kept, self.token_ids, text_threshold, remove_combined, self.tokenizer)
+            res.append((both[b, keep, T:], kept.max(dim=1)[0] if len(kept) else kept.new_zeros(0), phrases))
+        return res
 
     # ------------------------------------------------------------------ HIP graphs (latency mode)
     # At batch 1 the forward is ~600 small launches whose dependency chain is launch-latency-bound: 11.4 ms eager
@@ -649,14 +758,14 @@ class GDinoEngine:
             ops.layernorm_rows(src, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, out=vn, out2=s16)
             qv = ops.gemm(s16, w[d + ".fu.qv.w"], w[d + ".fu.qv.b"], out_dtype=F16)
             kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"], out_dtype=F16)
-            ov, ol = ops.biattn_fusion(qv, kl, B, S, T, 256 ** -0.5)
+            ov, ol = self._biattn(qv, kl, B, S, T, 256 ** -0.5)
             src = ops.gemm(ov, w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], col_scale=w[d + ".fu.gv"], residual=vn, out=vn)
         text = ops.gemm(ol, w[d + ".fu.outl.w"], w[d + ".fu.outl.b"], col_scale=w[d + ".fu.gl"], residual=ln32)
         # --- text enhancer (transformer_vanilla.py:101-123), 4 heads x 64, block-diagonal mask
         qk = ops.gemm(ops.add_cvt_f16(text, self.pos_text), w[d + ".txt.qk.w"], w[d + ".txt.qk.b"], out_dtype=F16)
         vv = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.v.w"], w[d + ".txt.v.b"], out_dtype=F16)
-        a = ops.attn_fewkeys(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
-                             blocked=self.text_blocked)
+        a = self._text_attn(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
+                            blocked=self.text_blocked)
         text = ops.layernorm_rows(ops.gemm(a, w[d + ".txt.out.w"], w[d + ".txt.out.b"], residual=text),
                                   w[d + ".txt.norm1.w"], w[d + ".txt.norm1.b"], 1e-5, out_dtype=F32)
         ff = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.lin1.w"], w[d + ".txt.lin1.b"], act="relu", out_dtype=F16)
@@ -698,12 +807,17 @@ class GDinoEngine:
         omn16 = torch.empty((B * S, 256), device=dev, dtype=F16)
         omn = ops.layernorm_rows(om, w["enc_output_norm.w"], w["enc_output_norm.b"], 1e-5, out=om, out2=omn16)
         text16 = ops.add_cvt_f16(text)
-        logits = torch.empty((B, S, T), device=dev, dtype=F32)
+        Tc, tw16, tbias = self.Tc, text16, self.logit_bias
+        if Tc != T:          # zero text rows with bias -inf (set_text): a pad column is never a row's maximum
+            tw16 = torch.zeros((B, Tc, 256), device=dev, dtype=F16)
+            tw16[:, :T] = text16.view(B, T, 256)
+            tw16 = tw16.view(B * Tc, 256)
+        logits = torch.empty((B, S, Tc), device=dev, dtype=F32)
         for b in range(B):   # ContrastiveEmbed: per-image "weights" = that image's text features
-            ops.gemm(omn16[b * S:(b + 1) * S], text16[b * T:(b + 1) * T], out=logits[b])
+            ops.gemm(omn16[b * S:(b + 1) * S], tw16[b * Tc:(b + 1) * Tc], tbias, out=logits[b])
         idx = ops.topk_rowmax(logits, nq)
         if stages is not None:
-            stages["topk_logits"] = logits
+            stages["topk_logits"] = logits if Tc == T else logits[:, :, :T]
             if "force_topk" in stages:                       # test hook: isolate the decoder from tie order
                 idx = stages["force_topk"].to(I32).to(dev).contiguous()
         sel16 = ops.gather_rows(omn, idx, B, nq, x_batch_rows=S, idx_batch_stride=nq)
@@ -730,10 +844,10 @@ class GDinoEngine:
                     stages["refs"].append(ops.box_refine(self._mlp3("box", ops.add_cvt_f16(output)), ref))
                 hs16 = ops.layernorm_rows(output, w["dec.norm.w"], w["dec.norm.b"], 1e-5)
         boxes = ops.box_refine(self._mlp3("box", hs16), ref).view(B, nq, 4)
-        out_logits = torch.empty((B, nq, T), device=dev, dtype=F32)
+        out_logits = torch.empty((B, nq, Tc), device=dev, dtype=F32)
         for b in range(B):
-            ops.gemm(hs16[b * nq:(b + 1) * nq], text16[b * T:(b + 1) * T], out=out_logits[b])
-        return out_logits, boxes
+            ops.gemm(hs16[b * nq:(b + 1) * nq], tw16[b * Tc:(b + 1) * Tc], tbias, out=out_logits[b])
+        return (out_logits if Tc == T else out_logits[:, :, :T]), boxes
 
     def _dec_layer(self, i: int, output: torch.Tensor, ref: torch.Tensor, mem16: torch.Tensor, text16: torch.Tensor,
                    pl: _Plan, B: int) -> torch.Tensor:
@@ -755,7 +869,7 @@ class GDinoEngine:
         # text cross-attention (keys/values = the T text tokens)
         q = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".ca.q.w"], w[d + ".ca.q.b"], out_dtype=F16)
         kv = ops.gemm(text16, w[d + ".ca.kv.w"], w[d + ".ca.kv.b"], out_dtype=F16)
-        a = ops.attn_fewkeys(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
+        a = self._text_attn(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
         output = ops.layernorm_rows(ops.gemm(a, w[d + ".ca.out.w"], w[d + ".ca.out.b"], residual=output),
                                     w[d + ".canorm.w"], w[d + ".canorm.b"], 1e-5, out_dtype=F32)
         # deformable cross-attention into the encoder memory (4-d reference boxes)

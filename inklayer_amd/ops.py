@@ -855,6 +855,22 @@ def biattn_fusion(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, T: int
     return out_v, out_l
 
 
+def biattn_wide(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, T: int, scale: float):
+    """biattn_fusion's semantics for 1 <= T <= 256 text tokens on f16 MFMA (csrc/biattn_wide.hip): qv16 f16 [B*S, 2048],
+    kl16 f16 [B*T, 2048] -> (out_v f16 [B*S, 1024], out_l f16 [B*T, 1024]).  No score matrix in HBM."""
+    assert qv16.dtype == F16 and qv16.is_contiguous() and kl16.dtype == F16 and kl16.is_contiguous()
+    assert tuple(qv16.shape) == (B * S, 2048) and tuple(kl16.shape) == (B * T, 2048)
+    dev = qv16.device
+    need = C.c_int64(0)
+    check(_lib.lib().ink_biattn_wide_workspace(B, S, T, C.byref(need)), "ink_biattn_wide_workspace")
+    ws = torch.empty(need.value, device=dev, dtype=F32)
+    out_v = torch.empty((B * S, 1024), device=dev, dtype=F16)
+    out_l = torch.empty((B * T, 1024), device=dev, dtype=F16)
+    check(_lib.lib().ink_biattn_wide(qv16.data_ptr(), kl16.data_ptr(), B, S, T, 1024, scale, ws.data_ptr(),
+                                     out_v.data_ptr(), out_l.data_ptr(), _stream()), "ink_biattn_wide")
+    return out_v, out_l
+
+
 def fusion_fold(v: torch.Tensor, B: int, S: int, lnv_g: torch.Tensor, lnv_b: torch.Tensor, eps: float,
                 text_kv: torch.Tensor, T: int, Wqv: torch.Tensor, bqv: torch.Tensor, Wo: torch.Tensor, bo: torch.Tensor,
                 gamma_v: torch.Tensor, scale: float, pos: Optional[torch.Tensor] = None,
@@ -1008,6 +1024,23 @@ def attn_fewkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n
                                       v.stride(0), B, n_q, n_k, n_heads, head_dim, scale, _p(blocked),
                                       _p(q_batch_rows), _p(q_add), int(io == F32), out.data_ptr(), out.stride(0), _stream()),
           "ink_attn_fewkeys")
+    return out
+
+
+def attn_midkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n_heads: int, head_dim: int,
+                 scale: float, blocked: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_fewkeys' contract for n_k <= 256 keys per batch entry on f16 rows (head_dim 32, 64; f32 math); a fully
+    blocked row gives zeros."""
+    for t in (q, k, v):
+        assert t.dtype == F16 and t.dim() == 2 and t.stride(1) == 1
+        assert t.data_ptr() % 16 == 0                      # 16-byte vector loads (the row strides: ld % 8 in the C entry)
+    n_q, n_k = q.shape[0] // B, k.shape[0] // B
+    out = torch.empty((B * n_q, n_heads * head_dim), device=q.device, dtype=F16)
+    if blocked is not None:
+        assert blocked.dtype == torch.uint8 and blocked.is_contiguous() and blocked.shape == (n_q, n_k)
+    check(_lib.lib().ink_attn_midkeys(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                      B, n_q, n_k, n_heads, head_dim, scale, _p(blocked), out.data_ptr(),
+                                      out.stride(0), _stream()), "ink_attn_midkeys")
     return out
 
 
