@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define INK_ABI_VERSION 9
+#define INK_ABI_VERSION 10
 int ink_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -359,15 +359,6 @@ int ink_gather_rows(const float* x, int64_t ldx, int64_t x_batch_rows, const int
                     int64_t idx_batch_stride, int32_t rows_per_batch, int32_t B, int32_t C,
                     void* out_f16, float* out_f32, void* stream);
 
-/* BiMultiHeadAttention core (GD/.../fuse_modules.py:168-240), both directions, no score matrix in
- * HBM beyond [B,S,4,T] f32:  QV f16 [B*S, 2E] = [v_proj(v) | values_v_proj(v)],
- * KL f16 [B*T, 2E] = [l_proj(l) | values_l_proj(l)], E = 1024 (4 heads x 256), T <= 4.
- * out_v f16 [B*S, E] (softmax over text), out_l f16 [B*T, E] (softmax over image tokens).
- * Workspaces: scores_ws f32 [B*S*4*T], stats_ws f32 [B*4*T*2], partial_ws f32 [B*4*ceil(S/chunk)*T*256]. */
-int ink_biattn_fusion(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, int32_t E,
-                      float scale, float* scores_ws, float* stats_ws, float* partial_ws, int32_t chunk,
-                      void* out_v_f16, void* out_l_f16, void* stream);
-
 /* softmax(scale q k^T [+ blocked -> -inf]) v against n_k <= 16 keys; head h at columns
  * [h*hd,(h+1)*hd); blocked: u8 [n_q, n_k] (1 = not allowed) or NULL.  io_f32 = 0: Q/K/V/O are f16 rows, hd in {32,64};
  * 1: f32 rows, hd in {16,32} (ld* in elements either way; the math is f32 in both).  q_batch_rows (int32 [B] or NULL):
@@ -391,8 +382,10 @@ int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
                      int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale, const uint8_t* blocked,
                      void* O, int64_t ldo, void* stream);
 
-/* ink_biattn_fusion's semantics for 1 <= T <= 256 text tokens on f16 MFMA (csrc/biattn_wide.hip): QV f16 [B*S, 2E],
- * KL f16 [B*T, 2E], E = 1024, S <= 32768; out_v f16 [B*S, E], out_l f16 [B*T, E].  No score matrix in HBM: the text side is
+/* BiMultiHeadAttention core (GD/.../fuse_modules.py:168-240), both directions, for 1 <= T <= 256 text tokens on f16 MFMA
+ * (csrc/biattn_wide.hip): QV f16 [B*S, 2E] = [v_proj(v) | values_v_proj(v)], KL f16 [B*T, 2E] = [l_proj(l) |
+ * values_l_proj(l)], E = 1024 (4 heads x 256), S <= 32768; out_v f16 [B*S, E] (softmax over the text tokens), out_l f16
+ * [B*T, E] (softmax over the image tokens).  No score matrix in HBM: the text side is
  * a split over chunks of 1024 image tokens that recomputes the score tile, merged by a fourth kernel; no atomics, the
  * results of image b do not depend on B.  ws: f32 [ink_biattn_wide_workspace(B, S, T)] = with Tp = 32 ceil(T / 32):
  * B*4*(128 Tp + ceil(S/128) Tp + ceil(S/1024) Tp 258) floats.  Returns 1 with nothing launched for a null pointer, T

@@ -89,8 +89,6 @@ SIGNATURES = {
                            c_void_p, c_i64, c_void_p],
     "ink_gather_rows": [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p,
                         c_void_p],
-    "ink_biattn_fusion": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                          c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "ink_biattn_colstats": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ink_fusion_fold_workspace": [c_int, c_int, C.POINTER(c_i64)],
     "ink_relpos_bias64_f16": [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],

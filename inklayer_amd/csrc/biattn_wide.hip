@@ -1,6 +1,6 @@
-// BiMultiHeadAttention core (fuse_modules.py:168-240) for captions of up to 256 tokens: ink_biattn_wide.
+// BiMultiHeadAttention core (fuse_modules.py:168-240), both directions, for captions of 1 to 256 tokens:
+// ink_biattn_wide, the fusion layer's general kernel (fusion_fold.hip is the specialisation for T <= 4).
 //
-// Same semantics as ink_biattn_fusion (detector_ops.hip), which keeps serving T <= 4:
 //   QV f16 [B*S, 2E] = [v_proj(v) | values_v_proj(v)],  KL f16 [B*T, 2E] = [l_proj(l) | values_l_proj(l)],
 //   E = 1024 = 4 heads x 256, score[s,h,t] = scale * q[s,h,:] . k[t,h,:],
 //   out_v[s,h,:] = sum_t softmax_t(score)[t] * values_l[t,h,:]      (image side, softmax over the T text tokens)

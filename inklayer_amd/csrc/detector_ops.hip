@@ -1,6 +1,6 @@
 // Small GroundingDINO-side kernels (HBM / latency bound): Swin patch gather, patch-merge LayerNorm,
-// GroupNorm, bi-directional image<->text fusion attention, top-k query selection, sine position embedding of boxes,
-// iterative box refinement.  (The text attentions against a handful of keys are in attn_few.hip.)
+// GroupNorm, top-k query selection, sine position embedding of boxes, iterative box refinement.  (The text attentions
+// against a handful of keys are in attn_few.hip, the image<->text fusion attention in fusion_fold.hip / biattn_wide.hip.)
 #include "common.h"
 #include "../../include/inklayer_hip.h"
 
@@ -162,198 +162,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// BiMultiHeadAttention, image side (fuse_modules.py:168-225): per image token s and head h
-//   score[s,h,t] = scale * q[s,h,:] . k[t,h,:]          (written out for the text side)
-//   out_v[s,h,:] = sum_t softmax_t(score)[t] * values_l[t,h,:]
-// QV f16 [B*S, 2E] = [v_proj(v) | values_v_proj(v)], KL f16 [B*T, 2E] = [l_proj(l) | values_l_proj(l)],
-// E = 1024 = 4 heads x 256.  One wave per token: lane owns 16 of the 1024 dims (head = lane/16).
-// The global max subtraction / +-50000 clamps of the reference are no-ops for a softmax unless
-// |score| > 5e4 (never for sane weights) and are not reproduced.
-template <int E>
-__global__ __launch_bounds__(256) void biattn_image_kernel(const f16* __restrict__ QV, const f16* __restrict__ KL,
-                                                           int B, int S, int T, float scale,
-                                                           float* __restrict__ scores, f16* __restrict__ out_v) {
-  constexpr int H = 4, HD = E / H, LD = 2 * E;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  f16* kl = (f16*)smem;                                   // [T][2E] of this image
-  const int b = blockIdx.y;
-  for (int i = threadIdx.x; i < T * LD / 8; i += 256)
-    ((f16x8*)kl)[i] = ((const f16x8*)(KL + (int64_t)b * T * LD))[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int h = lane / 16;
-  const int stride = gridDim.x * 4;
-  int s = blockIdx.x * 4 + wv;
-  f16x8 q0 = {0, 0, 0, 0, 0, 0, 0, 0}, q1 = q0;
-  if (s < S) {
-    const f16* qp = QV + ((int64_t)b * S + s) * LD + lane * 16;
-    q0 = *(const f16x8*)qp;
-    q1 = *(const f16x8*)(qp + 8);
-  }
-  for (; s < S; s += stride) {
-    // the next token's query row is fetched before this token's reductions (one token in flight per wave)
-    f16x8 n0 = q0, n1 = q1;
-    if (s + stride < S) {
-      const f16* np = QV + ((int64_t)b * S + s + stride) * LD + lane * 16;
-      n0 = *(const f16x8*)np;
-      n1 = *(const f16x8*)(np + 8);
-    }
-    float sc[16];
-    float mx = -3.0e38f;
-    for (int t = 0; t < T; ++t) {
-      const f16x8 k0 = *(const f16x8*)(kl + t * LD + lane * 16), k1 = *(const f16x8*)(kl + t * LD + lane * 16 + 8);
-      float d = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d = fmaf((float)q0[j], (float)k0[j], d);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d = fmaf((float)q1[j], (float)k1[j], d);
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);   // reduce over the head's 16 lanes
-      sc[t] = d * scale;
-      mx = fmaxf(mx, sc[t]);
-    }
-    if ((lane & 15) == 0)
-      for (int t = 0; t < T; ++t) scores[(((int64_t)b * S + s) * H + h) * T + t] = sc[t];
-    float sum = 0.f;
-    for (int t = 0; t < T; ++t) { sc[t] = expf(sc[t] - mx); sum += sc[t]; }
-    const float inv = 1.f / sum;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    for (int t = 0; t < T; ++t) {
-      const f16* vp = kl + t * LD + E + lane * 16;
-      const f16x8 v0 = *(const f16x8*)vp, v1 = *(const f16x8*)(vp + 8);
-      const float pw = sc[t] * inv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { acc[j] = fmaf(pw, (float)v0[j], acc[j]); acc[8 + j] = fmaf(pw, (float)v1[j], acc[8 + j]); }
-    }
-    f16x8 o0, o1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { o0[j] = (f16)acc[j]; o1[j] = (f16)acc[8 + j]; }
-    f16* op = out_v + ((int64_t)b * S + s) * E + lane * 16;
-    *(f16x8*)op = o0;
-    *(f16x8*)(op + 8) = o1;
-    q0 = n0;
-    q1 = n1;
-  }
-}
-
-// text side, pass 1a: per (b, row-chunk): partial max / sum-exp of every (h, t) column over the chunk's rows
-__global__ __launch_bounds__(256) void biattn_colstats_partial_kernel(const float* __restrict__ scores, int S,
-                                                                      int HT, int rows_per_chunk,
-                                                                      float* __restrict__ part) {
-  const int c = blockIdx.x, b = blockIdx.y, nchunk = gridDim.x;
-  const float* sp = scores + (int64_t)b * S * HT;
-  const int s0 = c * rows_per_chunk, s1 = min(S, s0 + rows_per_chunk);
-  __shared__ float red[4][2];
-  float mx[16], sm[16];
-  for (int k = 0; k < HT; ++k) { mx[k] = -3.0e38f; sm[k] = 0.f; }
-  for (int s = s0 + threadIdx.x; s < s1; s += 256)
-    for (int k = 0; k < HT; ++k) {
-      const float v = sp[(int64_t)s * HT + k];
-      if (v > mx[k]) { sm[k] = sm[k] * expf(mx[k] - v) + 1.f; mx[k] = v; } else { sm[k] += expf(v - mx[k]); }
-    }
-  for (int k = 0; k < HT; ++k) {
-    const float gm = wave_max(mx[k]);
-    const float gs = wave_sum(sm[k] * expf(mx[k] - gm));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = gm; red[threadIdx.x >> 6][1] = gs; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float M = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
-      float Ssum = 0.f;
-      for (int w = 0; w < 4; ++w) Ssum += red[w][1] * expf(red[w][0] - M);
-      part[(((int64_t)b * nchunk + c) * HT + k) * 2] = M;
-      part[(((int64_t)b * nchunk + c) * HT + k) * 2 + 1] = Ssum;
-    }
-  }
-}
-// pass 1b: combine the chunk partials -> stats[b][col] = (max, sum-exp)
-__global__ __launch_bounds__(64) void biattn_colstats_combine_kernel(const float* __restrict__ part, int nchunk,
-                                                                     int HT, float* __restrict__ stats) {
-  const int b = blockIdx.x, k = threadIdx.x;
-  if (k >= HT) return;
-  float M = -3.0e38f;
-  for (int c = 0; c < nchunk; ++c) M = fmaxf(M, part[(((int64_t)b * nchunk + c) * HT + k) * 2]);
-  float Ssum = 0.f;
-  for (int c = 0; c < nchunk; ++c)
-    Ssum += part[(((int64_t)b * nchunk + c) * HT + k) * 2 + 1] * expf(part[(((int64_t)b * nchunk + c) * HT + k) * 2] - M);
-  stats[((int64_t)b * HT + k) * 2] = M;
-  stats[((int64_t)b * HT + k) * 2 + 1] = Ssum;
-}
-
-// text side, pass 2: partial[b,h,chunk,t,d] = sum_{s in chunk} exp(score[s,h,t]-max) * values_v[s,h,d]
-// One workgroup per (chunk, batch): 128 threads x 8 consecutive value dims = the whole 1024-wide value half of a
-// row as ONE coalesced 2-KiB read (16 B per lane); the chunk's exp() values of all 4 heads are computed once into
-// LDS.  (The first version read one f16 per lane per row: 0.9 TB/s.)
-template <int E>
-__global__ __launch_bounds__(E / 8) void biattn_text_partial_kernel(const float* __restrict__ scores,
-                                                                    const float* __restrict__ stats,
-                                                                    const f16* __restrict__ QV, int S, int T,
-                                                                    int chunk, float* __restrict__ partial) {
-  constexpr int H = 4, HD = E / H, LD = 2 * E, NTH = E / 8;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* pe = (float*)smem;                                 // [chunk][H][T]
-  const int nchunk = gridDim.x;
-  const int c = blockIdx.x, b = blockIdx.y;
-  const int d0 = threadIdx.x * 8, h = d0 / HD;              // this thread's 8 dims sit inside head h
-  const int s0 = c * chunk, s1 = min(S, s0 + chunk);
-  const int HT = H * T;
-  for (int i = threadIdx.x; i < (s1 - s0) * HT; i += NTH) {
-    const int r = i / HT, k = i % HT;                       // k = head * T + t: the layout of a scores row
-    pe[i] = expf(scores[((int64_t)b * S + s0 + r) * HT + k] - stats[((int64_t)b * HT + k) * 2]);
-  }
-  __syncthreads();
-  float acc[4][8];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
-  const f16* vp = QV + ((int64_t)b * S + s0) * LD + E + d0;
-  const int n = s1 - s0;
-  auto accum = [&](int s, const f16x8& v) {
-    const float* pr = pe + s * HT + h * T;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (t < T) {
-        const float w = pr[t];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[t][j] = fmaf(w, (float)v[j], acc[t][j]);
-      }
-    }
-  };
-  int s = 0;
-  for (; s + 8 <= n; s += 8) {                              // eight rows in flight per thread
-    f16x8 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = *(const f16x8*)(vp + (int64_t)(s + u) * LD);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) accum(s + u, v[u]);
-  }
-  for (; s < n; ++s) accum(s, *(const f16x8*)(vp + (int64_t)s * LD));
-  const int dh = d0 % HD;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (t < T) {
-      float* o = partial + ((((int64_t)b * H + h) * nchunk + c) * T + t) * HD + dh;
-      *(f32x4*)o = (f32x4){acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
-      *(f32x4*)(o + 4) = (f32x4){acc[t][4], acc[t][5], acc[t][6], acc[t][7]};
-    }
-  }
-}
-// pass 3: out_l[b*T + t, h*HD + d] = sum_chunks partial / sumexp
-template <int E>
-__global__ __launch_bounds__(256) void biattn_text_reduce_kernel(const float* __restrict__ partial,
-                                                                 const float* __restrict__ stats, int T,
-                                                                 int nchunk, f16* __restrict__ out_l) {
-  constexpr int H = 4, HD = E / H;
-  const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-  float s = 0.f;
-  for (int c = 0; c < nchunk; ++c) s += partial[((((int64_t)b * H + h) * nchunk + c) * T + t) * HD + d];
-  out_l[((int64_t)b * T + t) * E + h * HD + d] = (f16)(s / stats[((int64_t)b * H * T + h * T + t) * 2 + 1]);
-}
-
-// ---------------------------------------------------------------------------------------------
 // Two-stage query selection: key[s] = max_t logits[b,s,t]; indices of the K largest, in descending
 // order, ties -> lower index (torch.topk leaves tie order unspecified).  One 1024-thread workgroup
 // per image, bitonic sort of 64-bit (ordered-value, index) keys in LDS (S <= 16384 -> 128 KiB).
@@ -506,43 +314,6 @@ extern "C" int ink_gather_rows(const float* x, int64_t ldx, int64_t x_batch_rows
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, idx,
                      idx_batch_stride, x_batch_rows, rows_per_batch, B, C, (f16*)out_f16, out_f32);
-  return ink_launch_status();
-}
-
-extern "C" int ink_biattn_fusion(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T,
-                                 int32_t E, float scale, float* scores_ws, float* stats_ws,
-                                 float* partial_ws, int32_t chunk, void* out_v_f16, void* out_l_f16,
-                                 void* stream) {
-  INK_CHECK_ARG(QV_f16 && KL_f16 && scores_ws && stats_ws && partial_ws && out_v_f16 && out_l_f16);
-  INK_CHECK_ARG(B > 0 && S > 0 && T > 0 && T <= 4 && E == 1024 && chunk > 0);   // H*T <= 16
-  hipStream_t s = (hipStream_t)stream;
-  const int lds = T * 2 * E * 2;
-  const int bx = (S + 3) / 4 < 512 ? (S + 3) / 4 : 512;
-  hipLaunchKernelGGL(biattn_image_kernel<1024>, dim3(bx, B), dim3(256), lds, s, (const f16*)QV_f16,
-                     (const f16*)KL_f16, B, S, T, scale, scores_ws, (f16*)out_v_f16);
-  const int nchunk = (S + chunk - 1) / chunk;
-  // column statistics: chunk partials are parked at the head of partial_ws (consumed before pass 2 rewrites it)
-  const int rows_cs = 512, ncs = (S + rows_cs - 1) / rows_cs;
-  INK_CHECK_ARG((int64_t)ncs * 4 * T * 2 <= (int64_t)4 * nchunk * T * 256);
-  hipLaunchKernelGGL(biattn_colstats_partial_kernel, dim3(ncs, B), dim3(256), 0, s, scores_ws, S, 4 * T, rows_cs,
-                     partial_ws);
-  hipLaunchKernelGGL(biattn_colstats_combine_kernel, dim3(B), dim3(64), 0, s, partial_ws, ncs, 4 * T, stats_ws);
-  hipLaunchKernelGGL(biattn_text_partial_kernel<1024>, dim3(nchunk, B), dim3(128), chunk * 4 * T * 4, s, scores_ws,
-                     stats_ws, (const f16*)QV_f16, S, T, chunk, partial_ws);
-  hipLaunchKernelGGL(biattn_text_reduce_kernel<1024>, dim3(T, 4, B), dim3(256), 0, s, partial_ws, stats_ws, T,
-                     nchunk, (f16*)out_l_f16);
-  return ink_launch_status();
-}
-
-// column (max, sum-exp) over the S rows of every image's [S, HT] score matrix (the text-side softmax statistics), also
-// used by the folded fusion layer (fusion_fold.hip).  part_ws: B * ceil(S / 512) * HT * 2 floats.
-extern "C" int ink_biattn_colstats(const float* scores, int32_t B, int32_t S, int32_t HT, float* part_ws, float* stats,
-                                   void* stream) {
-  INK_CHECK_ARG(scores && part_ws && stats && B > 0 && S > 0 && HT > 0 && HT <= 16);
-  hipStream_t s = (hipStream_t)stream;
-  const int rows_cs = 512, ncs = (S + rows_cs - 1) / rows_cs;
-  hipLaunchKernelGGL(biattn_colstats_partial_kernel, dim3(ncs, B), dim3(256), 0, s, scores, S, HT, rows_cs, part_ws);
-  hipLaunchKernelGGL(biattn_colstats_combine_kernel, dim3(B), dim3(64), 0, s, (const float*)part_ws, ncs, HT, stats);
   return ink_launch_status();
 }
 

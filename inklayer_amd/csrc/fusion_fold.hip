@@ -17,7 +17,7 @@
 // and written twice per layer (2 x 1 KiB in, 2 x 1 KiB out) instead of ~10 KiB per token.
 //   fuse_prep_kernel       U, c, Z from the text projections            (tiny: 16 x 256 x 256 MACs per image)
 //   fuse_ln_scores_kernel  vn = LN(v) (in place), scores = vn U^T + c   (one wave per token)
-//   biattn_colstats_*      column max / sum-exp over the image tokens   (detector_ops.hip, unchanged)
+//   biattn_colstats_*      column max / sum-exp over the image tokens   (two passes, ink_biattn_colstats)
 //   fuse_apply_kernel      v = vn + gamma_v (p_v Z + bo) (in place); partial weighted sums of vn for the text side
 //   fuse_text_kernel       m = sum of the partials; out_l = Wvv_h m + bvv_h  -> the text-side output projection input
 // The reference's global max subtraction / +-50000 clamps (fuse_modules.py:181-202) are no-ops for a softmax and are not
@@ -236,6 +236,50 @@ __global__ __launch_bounds__(1024) void fuse_text_kernel(const float* __restrict
   out_l[((int64_t)b * T + t) * (FH * FHD) + h * FHD + i] = (f16)o;
 }
 
+// text side, pass 1a: per (b, row-chunk): partial max / sum-exp of every (h, t) column over the chunk's rows
+__global__ __launch_bounds__(256) void biattn_colstats_partial_kernel(const float* __restrict__ scores, int S,
+                                                                      int HT, int rows_per_chunk,
+                                                                      float* __restrict__ part) {
+  const int c = blockIdx.x, b = blockIdx.y, nchunk = gridDim.x;
+  const float* sp = scores + (int64_t)b * S * HT;
+  const int s0 = c * rows_per_chunk, s1 = min(S, s0 + rows_per_chunk);
+  __shared__ float red[4][2];
+  float mx[16], sm[16];
+  for (int k = 0; k < HT; ++k) { mx[k] = -3.0e38f; sm[k] = 0.f; }
+  for (int s = s0 + threadIdx.x; s < s1; s += 256)
+    for (int k = 0; k < HT; ++k) {
+      const float v = sp[(int64_t)s * HT + k];
+      if (v > mx[k]) { sm[k] = sm[k] * expf(mx[k] - v) + 1.f; mx[k] = v; } else { sm[k] += expf(v - mx[k]); }
+    }
+  for (int k = 0; k < HT; ++k) {
+    const float gm = wave_max(mx[k]);
+    const float gs = wave_sum(sm[k] * expf(mx[k] - gm));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = gm; red[threadIdx.x >> 6][1] = gs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float M = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
+      float Ssum = 0.f;
+      for (int w = 0; w < 4; ++w) Ssum += red[w][1] * expf(red[w][0] - M);
+      part[(((int64_t)b * nchunk + c) * HT + k) * 2] = M;
+      part[(((int64_t)b * nchunk + c) * HT + k) * 2 + 1] = Ssum;
+    }
+  }
+}
+// pass 1b: combine the chunk partials -> stats[b][col] = (max, sum-exp)
+__global__ __launch_bounds__(64) void biattn_colstats_combine_kernel(const float* __restrict__ part, int nchunk,
+                                                                     int HT, float* __restrict__ stats) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (k >= HT) return;
+  float M = -3.0e38f;
+  for (int c = 0; c < nchunk; ++c) M = fmaxf(M, part[(((int64_t)b * nchunk + c) * HT + k) * 2]);
+  float Ssum = 0.f;
+  for (int c = 0; c < nchunk; ++c)
+    Ssum += part[(((int64_t)b * nchunk + c) * HT + k) * 2 + 1] * expf(part[(((int64_t)b * nchunk + c) * HT + k) * 2] - M);
+  stats[((int64_t)b * HT + k) * 2] = M;
+  stats[((int64_t)b * HT + k) * 2 + 1] = Ssum;
+}
+
 }  // namespace
 
 extern "C" int ink_fusion_fold_workspace(int32_t B, int32_t S, int64_t* out_floats) {
@@ -247,9 +291,17 @@ extern "C" int ink_fusion_fold_workspace(int32_t B, int32_t S, int64_t* out_floa
   return INK_OK;
 }
 
-// forward declarations of the column-statistics passes shared with the unfolded path (detector_ops.hip)
+// column (max, sum-exp) over the S rows of every image's [S, HT] score matrix: the text-side softmax statistics.
+// part_ws: B * ceil(S / 512) * HT * 2 floats.
 extern "C" int ink_biattn_colstats(const float* scores, int32_t B, int32_t S, int32_t HT, float* part_ws, float* stats,
-                                   void* stream);
+                                   void* stream) {
+  INK_CHECK_ARG(scores && part_ws && stats && B > 0 && S > 0 && HT > 0 && HT <= 16);
+  hipStream_t s = (hipStream_t)stream;
+  const int rows_cs = 512, ncs = (S + rows_cs - 1) / rows_cs;
+  hipLaunchKernelGGL(biattn_colstats_partial_kernel, dim3(ncs, B), dim3(256), 0, s, scores, S, HT, rows_cs, part_ws);
+  hipLaunchKernelGGL(biattn_colstats_combine_kernel, dim3(B), dim3(64), 0, s, (const float*)part_ws, ncs, HT, stats);
+  return ink_launch_status();
+}
 
 extern "C" int ink_fusion_fold(float* v_f32, int32_t B, int32_t S, const float* lnv_g, const float* lnv_b, float eps,
                                const float* text_k_f32, const float* text_vl_f32, int64_t ld_text, int32_t T,

@@ -384,7 +384,7 @@ def clean_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 class GDinoEngine:
     fuse_ffn = True          # encoder FFN + norm2 as one kernel (csrc/ffn_fused.hip); False: two GEMMs + LayerNorm
     fuse_ffn_pre = True      # ... starting at the deformable attention's output projection (out_proj + norm1 inside)
-    fold_fusion = True       # the caption's tokens folded through the fusion layers (csrc/fusion_fold.hip); False: rounds 1-2 path
+    fold_fusion = True       # a caption of <= 4 tokens folded through the fusion layers (csrc/fusion_fold.hip); False: the general kernel, csrc/biattn_wide.hip
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: Optional[GDinoConfig] = None,
                  device: str | torch.device = "cuda", encoded_text: Optional[torch.Tensor] = None,
@@ -539,9 +539,9 @@ class GDinoEngine:
         self._seen.clear()
         self.T = T
         self.token_ids = tuple(int(t) for t in token_ids)
-        # dispatch on T alone: <= 4 tokens take the folded / VALU fusion kernels, more the MFMA one (csrc/biattn_wide.hip);
-        # the text attentions keep their scores in registers up to 16 keys (csrc/attn_few.hip)
-        self._biattn = ops.biattn_fusion if T <= 4 else ops.biattn_wide
+        # dispatch on T alone: _enc_layer folds <= 4 tokens through the fusion layer and runs the general kernel
+        # (csrc/biattn_wide.hip) otherwise; the text attentions keep their scores in registers up to 16 keys
+        # (csrc/attn_few.hip)
         self._text_attn = ops.attn_fewkeys if T <= 16 else ops.attn_midkeys
         self.text0 = encoded_text.detach().to(self.dev, F32).contiguous()
         self._captions.put(self.token_ids, encoded_text.detach().to("cpu", F32))    # set_caption finds it again
@@ -758,7 +758,7 @@ class GDinoEngine:
             ops.layernorm_rows(src, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, out=vn, out2=s16)
             qv = ops.gemm(s16, w[d + ".fu.qv.w"], w[d + ".fu.qv.b"], out_dtype=F16)
             kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"], out_dtype=F16)
-            ov, ol = self._biattn(qv, kl, B, S, T, 256 ** -0.5)
+            ov, ol = ops.biattn_wide(qv, kl, B, S, T, 256 ** -0.5)
             src = ops.gemm(ov, w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], col_scale=w[d + ".fu.gv"], residual=vn, out=vn)
         text = ops.gemm(ol, w[d + ".fu.outl.w"], w[d + ".fu.outl.b"], col_scale=w[d + ".fu.gl"], residual=ln32)
         # --- text enhancer (transformer_vanilla.py:101-123), 4 heads x 64, block-diagonal mask

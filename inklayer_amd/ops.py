@@ -838,26 +838,11 @@ def gather_rows(x: torch.Tensor, idx: torch.Tensor, B: int, rows_per_batch: int,
     return out
 
 
-def biattn_fusion(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, T: int, scale: float,
-                  chunk: int = 128):
-    assert qv16.dtype == F16 and qv16.is_contiguous() and kl16.dtype == F16 and kl16.is_contiguous()
-    E = qv16.shape[1] // 2
-    dev = qv16.device
-    nchunk = -(-S // chunk)
-    scores = torch.empty(B * S * 4 * T, device=dev, dtype=F32)
-    stats = torch.empty(B * 4 * T * 2, device=dev, dtype=F32)
-    partial = torch.empty(B * 4 * nchunk * T * 256, device=dev, dtype=F32)
-    out_v = torch.empty((B * S, E), device=dev, dtype=F16)
-    out_l = torch.empty((B * T, E), device=dev, dtype=F16)
-    check(_lib.lib().ink_biattn_fusion(qv16.data_ptr(), kl16.data_ptr(), B, S, T, E, scale, scores.data_ptr(),
-                                       stats.data_ptr(), partial.data_ptr(), chunk, out_v.data_ptr(),
-                                       out_l.data_ptr(), _stream()), "ink_biattn_fusion")
-    return out_v, out_l
-
-
 def biattn_wide(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, T: int, scale: float):
-    """biattn_fusion's semantics for 1 <= T <= 256 text tokens on f16 MFMA (csrc/biattn_wide.hip): qv16 f16 [B*S, 2048],
-    kl16 f16 [B*T, 2048] -> (out_v f16 [B*S, 1024], out_l f16 [B*T, 1024]).  No score matrix in HBM."""
+    """BiMultiHeadAttention's core, both directions, for 1 <= T <= 256 text tokens on f16 MFMA (csrc/biattn_wide.hip):
+    qv16 f16 [B*S, 2048] = [v_proj(v) | values_v_proj(v)], kl16 f16 [B*T, 2048] = [l_proj(l) | values_l_proj(l)], 4 heads
+    x 256 -> (out_v f16 [B*S, 1024], softmax over the text tokens; out_l f16 [B*T, 1024], softmax over the image
+    tokens).  No score matrix in HBM."""
     assert qv16.dtype == F16 and qv16.is_contiguous() and kl16.dtype == F16 and kl16.is_contiguous()
     assert tuple(qv16.shape) == (B * S, 2048) and tuple(kl16.shape) == (B * T, 2048)
     dev = qv16.device

@@ -131,17 +131,17 @@ def test_set_text_truncates_at_256_tokens():
     assert eng.T == 256 and eng.token_ids == tuple(ids[:256]) and len(eng._graphs) == 0
     assert tuple(eng.text0.shape) == (256, 256) and tuple(eng.text_blocked.shape) == (256, 256)
     assert tuple(eng.pos_text.shape) == (256, 256)
-    assert eng._biattn.__name__ == "biattn_wide" and eng._text_attn.__name__ == "attn_midkeys"
+    assert eng._text_attn.__name__ == "attn_midkeys"
     m, _ = gdino.text_masks_and_position_ids(ids[:256])
     assert torch.equal(eng.text_blocked.bool(), ~m)
     eng.set_caption(ids[:17], encoded_text=torch.randn(17, 256))
-    assert eng.T == 17 and eng._text_attn.__name__ == "attn_midkeys" and eng._biattn.__name__ == "biattn_wide"
+    assert eng.T == 17 and eng._text_attn.__name__ == "attn_midkeys"
     eng.set_caption(ids[:16], encoded_text=torch.randn(16, 256))
-    assert eng._text_attn.__name__ == "attn_fewkeys" and eng._biattn.__name__ == "biattn_wide"
+    assert eng.T == 16 and eng._text_attn.__name__ == "attn_fewkeys"
     eng.set_caption(ids[:5], encoded_text=torch.randn(5, 256))
-    assert eng._text_attn.__name__ == "attn_fewkeys" and eng._biattn.__name__ == "biattn_wide"
+    assert eng.T == 5 and eng._text_attn.__name__ == "attn_fewkeys"
     eng.set_caption(gdino.DEFAULT_TOKEN_IDS, encoded_text=torch.randn(4, 256))
-    assert eng.T == 4 and eng._biattn.__name__ == "biattn_fusion" and eng._text_attn.__name__ == "attn_fewkeys"
+    assert eng.T == 4 and eng.fold_fusion and eng._text_attn.__name__ == "attn_fewkeys"
     eng.set_caption(ids)                                       # the cache serves the truncated caption
     assert eng.T == 256
     with pytest.raises(ValueError):

@@ -96,22 +96,26 @@ def test_encoder_triple_matches_float64(dev, engines, hw, B, ids):
 
 
 @torch.no_grad()
-@pytest.mark.parametrize("flag", ["fuse_ffn_pre", "fuse_ffn", "fold_fusion"])
-def test_encoder_triple_other_branches_match_float64(dev, engines, flag):
+@pytest.mark.parametrize("flag,hw,B,ids", [("fuse_ffn_pre", BIG, 2, R.DEFAULT_IDS), ("fuse_ffn", BIG, 2, R.DEFAULT_IDS),
+                                           ("fold_fusion", BIG, 2, R.DEFAULT_IDS), ("fold_fusion", SMALL, 3, R.SHORT_IDS)],
+                         ids=["fuse_ffn_pre", "fuse_ffn", "fold_fusion", "fold_fusion-160x224-B3-T3"])
+def test_encoder_triple_other_branches_match_float64(dev, engines, flag, hw, B, ids):
     """The branches of _enc_layer the product flags switch off: out_proj GEMM + norm1 ahead of the fused FFN
-    (fuse_ffn_pre = False), the two-GEMM FFN + LayerNorm (fuse_ffn = False), the unfolded fusion layer with
-    biattn_fusion (fold_fusion = False).  One layer, B = 2, T = 4, the same bound."""
-    eng, _, _ = engines
-    src, text = _encoder_reference(BIG, 2, R.DEFAULT_IDS)[:2]
+    (fuse_ffn_pre = False), the two-GEMM FFN + LayerNorm (fuse_ffn = False), the unfolded fusion layer on the general
+    kernel biattn_wide (fold_fusion = False; also at a ragged T = 3, B = 3).  One layer, the same bound."""
+    eng, _, text0 = engines
+    src, text = _encoder_reference(hw, B, ids)[:2]
     cls = type(eng)
     assert getattr(cls, flag) is True and flag not in vars(eng)
     try:
         setattr(eng, flag, False)
-        outs = _run_encoder(eng, dev, BIG, 2, src, text, 1)
+        _with_ids(eng, text0, ids)
+        outs = _run_encoder(eng, dev, hw, B, src, text, 1)
     finally:
         delattr(eng, flag)
+        _with_ids(eng, text0, R.DEFAULT_IDS)
     assert getattr(eng, flag) is True
-    _hold_encoder(outs, BIG, 2, R.DEFAULT_IDS, f"encoder {flag}=False")
+    _hold_encoder(outs, hw, B, ids, f"encoder {flag}=False {hw} B={B} T={len(ids)}")
 
 
 @torch.no_grad()

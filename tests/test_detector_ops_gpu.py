@@ -910,68 +910,6 @@ def test_fusion_fold_images_are_independent(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# biattn_fusion (the fold_fusion = False path) at production S
-# ---------------------------------------------------------------------------------------------------------------
-_BIATTN = {}
-
-
-def _biattn_data(S):
-    if S not in _BIATTN:
-        _BIATTN.clear()
-        g = torch.Generator().manual_seed(S + 1)
-        _BIATTN[S] = (torch.randn(2 * S, 2048, generator=g).half(), torch.randn(2, 4, 2048, generator=g).half())
-    return _BIATTN[S]
-
-
-@torch.no_grad()
-@pytest.mark.parametrize("T", [1, 2, 3, 4])
-@pytest.mark.parametrize("S", [13294, 22223])
-def test_biattn_fusion_production_sizes(dev, S, T):
-    """ops.biattn_fusion, B = 2, f16 q / k / v against float64.  Scores: 16 exact f16 products per lane in an fma chain and
-    a 16-lane shuffle tree, ds <= 21 u scale |q|.|k|.  Image side: softmax over T (p off by ds_t + max ds + 4 u), T fmas
-    (<= (T + 1) u sum p|vl|), f16 store.  Text side: w = exp(s - M) off by ds + max ds + u|s - M| + 2 u; the weighted sum
-    runs 128 rows per chunk then the chunks (<= (130 + nchunk) u sum w|vv|); the sum-exp is combined from 512-row
-    chunks (<= (3 ncs + 40) u relative); division and f16 store."""
-    from inklayer_amd import ops
-    qv, kl4 = _biattn_data(S)
-    B, E, sc = 2, 1024, 256 ** -0.5
-    kl = kl4[:, :T].reshape(B * T, 2048)
-    ov, ol = ops.biattn_fusion(qv.to(dev), kl.to(dev), B, S, T, sc)
-    ov, ol = ov.double().cpu(), ol.double().cpu()
-    nchunk, ncs = -(-S // 128), -(-S // 512)
-    worst_v = worst_l = 0.0
-    for b in range(B):
-        sp = lambda x: x.double().view(-1, 4, 256).transpose(0, 1)                  # [4, n, 256]
-        q, vv = sp(qv[b * S:(b + 1) * S, :E]), sp(qv[b * S:(b + 1) * S, E:])
-        k, vl = sp(kl[b * T:(b + 1) * T, :E]), sp(kl[b * T:(b + 1) * T, E:])
-        s = sc * (q @ k.transpose(-1, -2))                                          # [4, S, T]
-        ds = 21 * U * sc * (q.abs() @ k.abs().transpose(-1, -2)) + U * s.abs()
-        p = s.softmax(-1)
-        rv = p @ vl
-        eps = ds + ds.amax(-1, keepdim=True) + 4 * U
-        tv = (p * eps) @ vl.abs() + (p * eps).sum(-1, keepdim=True) * rv.abs() + (T + 1) * U * (p @ vl.abs())
-        tv = tv + (2.0 ** -11 + 2 * U) * rv.abs() + 2.0 ** -25
-        st, dst = s.transpose(-1, -2), ds.transpose(-1, -2)                          # [4, T, S]
-        P = st.softmax(-1)
-        rl = P @ vv
-        e2 = dst + dst.amax(-1, keepdim=True) + U * (st - st.amax(-1, keepdim=True)).abs() + 2 * U
-        tl = ((130 + nchunk) * U * (P @ vv.abs()) + (P * e2) @ vv.abs()
-              + rl.abs() * ((P * e2).sum(-1, keepdim=True) + (3 * ncs + 40) * U))
-        tl = tl + (2.0 ** -11 + 2 * U) * rl.abs() + 2.0 ** -25
-        if b == 0:
-            pw = p.transpose(-1, -2)
-            _discriminates((pw / pw.sum(-1, keepdim=True)) @ vv, rl, tl,
-                           "text side weighted by the image-side softmax over T")
-        gv = ov[b * S:(b + 1) * S].view(S, 4, 256).transpose(0, 1)
-        gl = ol[b * T:(b + 1) * T].view(T, 4, 256).transpose(0, 1)
-        worst_v = max(worst_v, ((gv - rv).abs() / tv).max().item())
-        worst_l = max(worst_l, ((gl - rl).abs() / tl).max().item())
-        _assert_within(gv, rv, tv, f"biattn_fusion out_v S={S} T={T} image {b}")
-        _assert_within(gl, rl, tl, f"biattn_fusion out_l S={S} T={T} image {b}")
-    print(f"S={S} T={T}: out_v {worst_v:.3f}x, out_l {worst_l:.3f}x the bound")
-
-
-# ---------------------------------------------------------------------------------------------------------------
 # groupnorm_nhwc through the plan
 # ---------------------------------------------------------------------------------------------------------------
 @torch.no_grad()

@@ -53,7 +53,7 @@ def test_caption_stages_match_oracle(dev, caption_dino):
     from oracle import gdino_ref
     c = caption_dino
     sd, oc, eng, text, img = c["sd"], c["oc"], c["eng"], c["text23"], c["img"]
-    assert eng.T == 23 and eng._biattn.__name__ == "biattn_wide" and eng._text_attn.__name__ == "attn_midkeys"
+    assert eng.T == 23 and eng._text_attn.__name__ == "attn_midkeys"
     mean, std = torch.tensor([0.485, 0.456, 0.406]), torch.tensor([0.229, 0.224, 0.225])
     x = ((torch.from_numpy(img).permute(2, 0, 1).float() / 255.0) - mean.view(3, 1, 1)) / std.view(3, 1, 1)
     sm, pid = gdino_ref.text_masks_and_position_ids(list(IDS23))
@@ -159,7 +159,7 @@ def test_caption_switch_back_to_four_tokens_is_bitwise(dev, caption_dino):
     wide = eng.forward([dimg])
     assert tuple(wide[0].shape) == (1, 300, 23)
     eng.set_caption(IDS4, encoded_text=c["text4"])
-    assert eng._biattn.__name__ == "biattn_fusion" and eng._text_attn.__name__ == "attn_fewkeys"
+    assert eng.T == 4 and eng.fold_fusion and eng._text_attn.__name__ == "attn_fewkeys"
     for _ in range(3):
         got = eng.forward([dimg])
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
@@ -216,7 +216,7 @@ def test_plugin_predict_leaves_the_default_caption(dev, tmp_path, monkeypatch):
         eng.w["dec.norm.b"].mul_(0.05)
         before = DET.run_ft_dino_on_sketch(str(png))
         out = DET.run_gdino_on_sketch(str(png), ids, box_threshold=0.5, text_threshold=0.5)
-        assert tuple(eng.token_ids) == tuple(gdino.DEFAULT_TOKEN_IDS) and eng._biattn.__name__ == "biattn_fusion"
+        assert tuple(eng.token_ids) == tuple(gdino.DEFAULT_TOKEN_IDS) and eng.T == 4 and eng.fold_fusion
         after = DET.run_ft_dino_on_sketch(str(png))
         again = DET.run_gdino_on_sketch(str(png), ids, box_threshold=0.5, text_threshold=0.5)
         after2 = DET.run_ft_dino_on_sketch(str(png))

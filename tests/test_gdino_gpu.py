@@ -72,7 +72,7 @@ def test_fusion_fewkeys_groupnorm_ops(dev):
     B, S, T, E = 2, 1129, 4, 1024
     qv = torch.randn(B * S, 2 * E, generator=g).half()
     kl = torch.randn(B * T, 2 * E, generator=g).half()
-    ov, ol = ops.biattn_fusion(qv.to(dev), kl.to(dev), B, S, T, 256 ** -0.5)
+    ov, ol = ops.biattn_wide(qv.to(dev), kl.to(dev), B, S, T, 256 ** -0.5)
     q = qv[:, :E].double().view(B, S, 4, 256).transpose(1, 2)
     vv = qv[:, E:].double().view(B, S, 4, 256).transpose(1, 2)
     k = kl[:, :E].double().view(B, T, 4, 256).transpose(1, 2)

@@ -171,7 +171,7 @@ def test_inpaint_entry_points_reject_bad_arguments_without_launch():
     assert l.ink_inp_unsharp(p, 8, 8, 3, 15379114, 1, 150, 3, q, r, None) == 1   # fw is not (2^24 - ww) / 2
     assert l.ink_inp_unsharp(p, 8, 8, 2, 15379114, 699051, 150, 3, q, r, None) == 1
     assert l.ink_inp_rgba_cut(p, p, 0, 8, q, None) == 1
-    assert l.ink_abi_version() == 9
+    assert l.ink_abi_version() == 10
 
 
 def test_small_images_raise_value_error():

@@ -43,9 +43,9 @@ def test_backward_rejects_each_null_pointer():
                                                  a["L"], a["P"], a["step"], *ptrs[6:], None) == 1, i
 
 
-def test_abi_version_is_9():
+def test_abi_version_is_10():
     from inklayer_amd import _lib
-    assert _lib.lib().ink_abi_version() == 9
+    assert _lib.lib().ink_abi_version() == 10
     assert "ink_ms_deform_attn_forward_dev" in _lib.SIGNATURES and "ink_ms_deform_attn_backward_dev" in _lib.SIGNATURES
 
 

@@ -1,11 +1,10 @@
 """What a caption costs the detector (development aid; MI355X, one process).
 
 Reports, for 800 x 800 images and random weights (the time does not depend on them):
-  * detector forward, ms, at B = 1 and B = 8 for captions of T = 4 (both existing fusion paths: folded and
-    ops.biattn_fusion), 17, 64 and 256 tokens - eager, allow_graph=False, so that every T is measured the same way;
+  * detector forward, ms, at B = 1 and B = 8 for captions of T = 4 (both fusion paths: folded, and unfolded on
+    ops.biattn_wide), 17, 64 and 256 tokens - eager, allow_graph=False, so that every T is measured the same way;
   * ops.biattn_wide alone at S = 13294 for the same T, next to its byte floor: QV read twice for q (both passes) and
-    once for values_v, out_v written once - 8 KiB per image token - over 8 TB/s;
-  * ops.biattn_wide at T = 4 next to ops.biattn_fusion on the same inputs: the one yardstick that already exists.
+    once for values_v, out_v written once - 8 KiB per image token - over 8 TB/s.
 Every case is warmed up; the cases are then timed in alternation over several rounds with device events, and the
 median and the spread (min .. max) of the rounds are printed."""
 import statistics
@@ -68,11 +67,10 @@ def main(rounds: int = 7) -> None:
     g = torch.Generator(device=dev).manual_seed(0)
     qv = torch.randn((S, 2048), generator=g, device=dev).half()
     kls = {T: torch.randn((T, 2048), generator=g, device=dev).half() for T in TS}
-    cases = {f"biattn_wide   S={S} T={T}": (lambda T=T: ops.biattn_wide(qv, kls[T], 1, S, T, sc)) for T in TS}
-    cases[f"biattn_fusion S={S} T=4"] = lambda: ops.biattn_fusion(qv, kls[4], 1, S, 4, sc)
+    cases = {f"biattn_wide S={S} T={T}": (lambda T=T: ops.biattn_wide(qv, kls[T], 1, S, T, sc)) for T in TS}
     floor_ms = S * 8192 / HBM_BYTES_PER_S * 1e3
     show(f"bi-attention alone, B = 1 (byte floor: 8 KiB per image token = {floor_ms * 1e3:.1f} us)",
-         timed(cases, rounds, 20), {k: floor_ms for k in cases if k.startswith("biattn_wide")})
+         timed(cases, rounds, 20), {k: floor_ms for k in cases})
     del qv
     # ---- the detector forward
     for B in (1, 8):
@@ -83,7 +81,7 @@ def main(rounds: int = 7) -> None:
                 eng = gdino.GDinoEngine(sd, cfg, dev, encoded_text=weights_init.random_text_features(cfg, dev, n_tokens=T),
                                         token_ids=caption_ids(T))
                 eng.fold_fusion = fold
-                name = f"forward B={B} T={T}" + (" (folded)" if T == 4 and fold else " (biattn_fusion)" if T == 4 else "")
+                name = f"forward B={B} T={T}" + (" (folded)" if T == 4 and fold else " (biattn_wide)" if T == 4 else "")
                 engines[name] = eng
         cases = {name: (lambda e=e: e.forward(imgs, allow_graph=False)) for name, e in engines.items()}
         show(f"detector forward, {hw[0]} x {hw[1]}, eager", timed(cases, rounds, 3 if B == 1 else 1))

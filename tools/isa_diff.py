@@ -5,7 +5,8 @@
 Compiles every inklayer_amd/csrc/*.hip of each tree to device assembly with build.FLAGS, splits it per function, strips
 comments and mangled symbol names, and prints for every kernel its instruction count, its resource metadata and whether
 the two trees agree.  Compared are a function's text up to its end label (which holds its .amdhsa_kernel block, so
-accum_offset and every other directive too) and the metadata fields below.  Exits 1 if anything differs.  A refactor
+accum_offset and every other directive too) and the metadata fields below.  A kernel that moved to another file is
+followed by its name and printed as `old.hip->new.hip:kernel`.  Exits 1 if anything differs.  A refactor
 that only moves __forceinline__ code must come out `identical` everywhere; the tool looks for no particular instruction.
 """
 from __future__ import annotations
@@ -58,9 +59,28 @@ def tree(root: Path, tmp: Path) -> dict[str, tuple[list[str], dict[str, str]]]:
     return {f"{s.name}:{k}": v for s, t in zip(srcs, texts) for k, v in kernels(t).items()}
 
 
+def follow_moves(a: dict, b: dict) -> dict[str, str]:
+    """A kernel that left its file in A and whose name occurs once in each tree is compared with its namesake in B:
+    b is re-keyed in place, and {A's key: B's file} of those kernels is returned."""
+    def by_name(t):
+        out: dict[str, list[str]] = {}
+        for k in t:
+            out.setdefault(k.split(":", 1)[1], []).append(k)
+        return out
+    na, nb = by_name(a), by_name(b)
+    moved = {}
+    for n, ka in na.items():
+        kb = nb.get(n, [])
+        if len(ka) == 1 and len(kb) == 1 and ka[0] != kb[0]:
+            b[ka[0]] = b.pop(kb[0])
+            moved[ka[0]] = kb[0].split(":", 1)[0]
+    return moved
+
+
 def main() -> int:
     with tempfile.TemporaryDirectory() as d:
         a, b = tree(Path(sys.argv[1]), Path(d) / "a"), tree(Path(sys.argv[2]), Path(d) / "b")
+    moved = follow_moves(a, b)
     names = subprocess.run(["c++filt", "-p"], input="\n".join(k.split(":", 1)[1] for k in sorted(a.keys() | b.keys())),
                            capture_output=True, text=True).stdout.splitlines()
     bad = 0
@@ -71,7 +91,8 @@ def main() -> int:
         bad += not same
         count = lambda ls: sum(1 for l in ls if not l.startswith(".") and not l.endswith(":"))  # noqa: E731
         for ls, ms, tag in ((la, ma, "identical"),) if same else ((la, ma, "differs: A"), (lb, mb, "differs: B")):
-            print(f"{key.split(':')[0]}:{name.replace('(anonymous namespace)::', '')}  {count(ls)}  "
+            where = key.split(":")[0] + ("->" + moved[key] if key in moved else "")
+            print(f"{where}:{name.replace('(anonymous namespace)::', '')}  {count(ls)}  "
                   + " ".join(ms.get(k, "-") for k in META) + f"  {tag}")
     print(f"{len(names)} kernels, {bad} differ")
     return 1 if bad else 0
