@@ -7,7 +7,8 @@ HBM (the reference re-`.to(device)`s it every call, GD/util/inference.py:64).
 
 `predict(model, image, caption, box_threshold, text_threshold)` is the reference's open-vocabulary call
 (GD/util/inference.py:54-97): any caption of up to 256 tokens, a phrase per box.  `run_gdino_on_sketch` wraps it in
-run_ft_dino_on_sketch's dict shape with the real labels."""
+run_ft_dino_on_sketch's dict shape with the real labels.  `predict_batch` / `run_gdino_on_sketches` take a batch of
+images with one caption each and run it as one forward (per-image token counts and text padding masks)."""
 import os
 import re
 
@@ -148,6 +149,61 @@ def predict(model, image, caption, box_threshold, text_threshold, device="cuda",
         if tuple(model.token_ids) != held_ids:
             model.set_caption(held_ids)
         model.tokenizer = held_tok
+
+
+def predict_batch(model, images, captions, box_threshold, text_threshold, remove_combined=False):
+    """predict for a batch with ONE CAPTION PER IMAGE (GroundingDINO.forward with a list of captions): images are HWC
+    uint8 RGB arrays or paths, captions strs or sequences of token ids, one per image.  -> [(boxes, scores, phrases)] in
+    input order.  One forward for the batch (size groups for images of different sizes) on the engine's per-image form
+    (GDinoEngine.set_captions): every image is scored against its own caption only and pays for its own token count.
+    Stateless like predict: the engine leaves with the caption(s), features and tokenizer it came with."""
+    import torch
+    from inklayer_amd import gdino, ops
+    images, captions = list(images), list(captions)
+    if len(images) != len(captions):
+        raise ValueError(f"{len(images)} images for {len(captions)} captions: predict_batch takes one caption per image")
+    if not images:
+        return []
+    tok, id_lists = None, []
+    for c in captions:
+        ids, tok = _caption_ids(c)
+        id_lists.append(ids)
+    resized = []
+    for image in images:
+        if isinstance(image, (str, os.PathLike)):
+            image = np.asarray(Image.open(image).convert("RGB"))
+        raw = torch.from_numpy(np.ascontiguousarray(image)).to(model.dev)
+        oh, ow = gdino.resize_shape(image.shape[1], image.shape[0])
+        resized.append(ops.resize_bilinear_u8(raw, oh, ow))
+    texts = None
+    if os.environ.get("INKLAYER_RANDOM_WEIGHTS") == "1":      # no BERT weights: stand-in features per caption, as predict
+        from inklayer_amd import weights_init
+        texts = [weights_init.random_text_features(model.cfg, "cpu", n_tokens=min(len(ids), model.cfg.max_text_len))
+                 for ids in id_lists]
+    # the held state with its features: a batch of many captions may push them out of the engine's caption cache
+    held_tok, held_caps, held_ids, held_text = model.tokenizer, model.captions, model.token_ids, model.text0.cpu()
+    held_lens, held_tmax = model.t_lens, model.Tmax
+    try:
+        model.set_captions(id_lists, encoded_texts=texts)
+        model.tokenizer = tok
+        return model.predict(resized, box_threshold, text_threshold, remove_combined)
+    finally:
+        if held_caps is None:
+            model.set_caption(held_ids, encoded_text=held_text)
+        else:
+            rows = held_text.view(len(held_caps), held_tmax, 256)
+            model.set_captions(held_caps, encoded_texts=[rows[b, :n] for b, n in enumerate(held_lens)])
+        model.tokenizer = held_tok
+
+
+def run_gdino_on_sketches(paths, captions, box_threshold=0.2, text_threshold=0.0):
+    """run_gdino_on_sketch for a batch of sketches, each with its own caption: a list of run_ft_dino_on_sketch-shaped
+    dicts, in input order."""
+    out = []
+    for boxes, scores, phrases in predict_batch(get_model(), paths, captions, box_threshold, text_threshold):
+        normalized = cxcywh_to_xyxy(boxes.tolist()).tolist()
+        out.append({"bboxes": normalized, "scores": scores.tolist(), "labels": list(phrases)})
+    return out
 
 
 def run_gdino_on_sketch(sketch_path, caption, box_threshold=0.2, text_threshold=0.0):

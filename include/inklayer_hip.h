@@ -396,6 +396,33 @@ int ink_biattn_wide_workspace(int32_t B, int32_t S, int32_t T, int64_t* out_floa
 int ink_biattn_wide(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, int32_t E, float scale,
                     float* ws, void* out_v_f16, void* out_l_f16, void* stream);
 
+/* ink_biattn_wide with ONE TOKEN COUNT PER IMAGE: a batch whose captions differ in length, padded to Tmax rows each.
+ * It replaces the attention_mask_l arithmetic of fuse_modules.py:214-218 (masked_fill of the padded text columns with
+ * -inf before the image side's softmax); the text side's rows at padded tokens, which nothing reads, become zeros.
+ * t_len: int32 [B] ON THE DEVICE; image b's text rows are KL[b*Tmax .. b*Tmax + t_len[b]) and the kernels clamp
+ * t_len[b] into 1..Tmax themselves.  The pad rows of KL are never read; the rows t >= t_len[b] of out_l f16 [B*Tmax, E]
+ * are written as zeros.  Each workgroup takes its tile count from its own image's count, so that the results of
+ * image b are bitwise those of ink_biattn_wide(B = 1, T = t_len[b]) on that image's rows.  ws: f32
+ * [ink_biattn_wide_workspace(B, S, Tmax)].  Returns 1 with nothing launched for a null pointer (t_len included), Tmax
+ * outside 1..256, and everything ink_biattn_wide refuses.  (Two more entry points of ABI 10: nothing existing
+ * changes.) */
+int ink_biattn_wide_varlen(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t Tmax,
+                           const int32_t* t_len /* device, [B] */, int32_t E, float scale, float* ws,
+                           void* out_v_f16, void* out_l_f16 /* [B*Tmax, E] */, void* stream);
+
+/* ink_attn_midkeys with a mask and a key count per batch entry: the text attentions of a batch of padded captions.
+ * blocked: u8 [n_q, n_k] per entry, blocked_batch_stride BYTES apart (0: one shared matrix, as ink_attn_midkeys; NULL:
+ * none, and the stride must be 0) - the per-row self-attention masks bertwarper.py's
+ * generate_masks_with_special_tokens_and_transfer_map gives for padded ids (transformer_vanilla.py:114-116).  k_len:
+ * int32 [B] ON THE DEVICE or NULL: the keys t >= k_len[b] do not exist for entry b (key_padding_mask of
+ * transformer.py:903-909 and of the text enhancer); they are never loaded, so their content, NaN included, reaches no
+ * output.  The kernel clamps k_len[b] into 0..n_k; key rows stay at b*n_k + t.  A row with no allowed key gives zeros.
+ * Return codes and argument rules are those of ink_attn_midkeys; a negative stride returns 1. */
+int ink_attn_midkeys_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                            int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale,
+                            const uint8_t* blocked, int64_t blocked_batch_stride, const int32_t* k_len,
+                            void* O, int64_t ldo, void* stream);
+
 /* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
  * image: 7..16 x 4096, SA/modeling/transformer.py:163-168) on f32 rows: head h at columns [h*hd,(h+1)*hd), head_dim
  * must be 16 and n_heads a multiple of 4; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].

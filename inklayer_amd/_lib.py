@@ -112,6 +112,10 @@ SIGNATURES = {
     "ink_biattn_wide_workspace": [c_int, c_int, c_int, C.POINTER(c_i64)],
     "ink_biattn_wide": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                         c_void_p],
+    "ink_biattn_wide_varlen": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                               c_void_p, c_void_p],
+    "ink_attn_midkeys_varlen": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
+                                c_float, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p],
     "ink_attn_fewq": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
                       c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "ink_topk_rowmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

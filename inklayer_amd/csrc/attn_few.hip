@@ -98,19 +98,27 @@ __global__ __launch_bounds__(256) void attn_fewkeys_kernel(const T* __restrict__
 // rows.  Plain VALU, not MFMA: the work is about 0.24 GFLOP per image and decoder layer.  One thread per (batch, query,
 // head) as above, but the scores do not fit a register array, so the softmax is the online form over blocks of 8
 // keys: 8 independent dot products, one rescale of the accumulator per block.  f32 math.  A fully blocked row (it
-// cannot occur in the detector: a token always sees itself) gives zeros, not NaN.
+// cannot occur in the detector's shared-caption form: a token always sees itself) gives zeros, not NaN.
+// ink_attn_midkeys_varlen adds a mask per batch entry (blocked_stride bytes apart; 0: one shared mask) and a key
+// count per batch entry (k_len, clamped into 0..n_k here so that a bad device value cannot index out of range): the
+// keys t >= k_len[b] do not exist for entry b - the loop ends there and their rows are never loaded.  The key rows
+// stay at b n_k + t, so an entry's arithmetic is that of a uniform launch at n_k = k_len[b].
 template <int HD>
 __global__ __launch_bounds__(256) void attn_midkeys_kernel(const f16* __restrict__ Q, int64_t ldq,
                                                            const f16* __restrict__ K, int64_t ldk,
                                                            const f16* __restrict__ V, int64_t ldv, int B, int n_q,
                                                            int n_k, int n_heads, float scale,
-                                                           const uint8_t* __restrict__ blocked, f16* __restrict__ O,
+                                                           const uint8_t* __restrict__ blocked,
+                                                           int64_t blocked_stride,
+                                                           const int32_t* __restrict__ k_len, f16* __restrict__ O,
                                                            int64_t ldo) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (int64_t)B * n_q * n_heads) return;
   const int h = (int)(gid % n_heads);
   const int64_t bq = gid / n_heads;
   const int b = (int)(bq / n_q), q = (int)(bq % n_q);
+  const int nk = k_len ? min(max(k_len[b], 0), n_k) : n_k;  // this entry's keys
+  const uint8_t* brow = blocked ? blocked + b * blocked_stride + (int64_t)q * n_k : nullptr;
   float qv[HD];
   const f16* qp = Q + bq * ldq + h * HD;
 #pragma unroll
@@ -119,14 +127,14 @@ __global__ __launch_bounds__(256) void attn_midkeys_kernel(const f16* __restrict
 #pragma unroll
   for (int i = 0; i < HD; ++i) acc[i] = 0.f;
   float m = -3.0e38f, l = 0.f;
-  for (int t0 = 0; t0 < n_k; t0 += 8) {
+  for (int t0 = 0; t0 < nk; t0 += 8) {
     float sc[8];
     float bm = -3.0e38f;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int t = t0 + u;
       float d = -3.0e38f;
-      if (t < n_k && !(blocked && blocked[q * n_k + t])) {
+      if (t < nk && !(brow && brow[t])) {
         const f16* kp = K + ((int64_t)b * n_k + t) * ldk + h * HD;
         d = 0.f;
 #pragma unroll
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(256) void attn_midkeys_kernel(const f16* __restrict
       sc[u] = d;
       bm = fmaxf(bm, d);
     }
-    if (bm <= -1.0e38f) continue;                           // the whole block is blocked or past n_k
+    if (bm <= -1.0e38f) continue;                           // the whole block is blocked or past nk
     const float mn = fmaxf(m, bm);
     const float a = expf(m - mn);                           // first live block: exp(-3e38 - mn) = 0 on acc = 0
     l *= a;
@@ -474,10 +482,11 @@ extern "C" int ink_attn_fewkeys(const void* Q, int64_t ldq, const void* K, int64
   return ink_launch_status();
 }
 
-extern "C" int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
-                                int64_t ldv, int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads,
-                                int32_t head_dim, float scale, const uint8_t* blocked, void* O, int64_t ldo,
-                                void* stream) {
+// both entry points of attn_midkeys_kernel: k_len == nullptr and blocked_stride == 0 is the uniform form
+static int midkeys_launch(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                          int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads, int32_t head_dim, float scale,
+                          const uint8_t* blocked, int64_t blocked_stride, const int32_t* k_len, void* O, int64_t ldo,
+                          void* stream) {
   INK_CHECK_ARG(Q && K && V && O && B > 0 && n_q > 0 && n_k > 0 && n_k <= 256 && n_heads > 0);
   INK_CHECK_ARG(head_dim == 32 || head_dim == 64);
   INK_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
@@ -486,10 +495,29 @@ extern "C" int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define INK_MIDKEYS(HD)                                                                                            \
   hipLaunchKernelGGL(attn_midkeys_kernel<HD>, grid, block, 0, (hipStream_t)stream, (const f16*)Q, ldq,             \
-                     (const f16*)K, ldk, (const f16*)V, ldv, B, n_q, n_k, n_heads, scale, blocked, (f16*)O, ldo)
+                     (const f16*)K, ldk, (const f16*)V, ldv, B, n_q, n_k, n_heads, scale, blocked, blocked_stride, \
+                     k_len, (f16*)O, ldo)
   if (head_dim == 32) INK_MIDKEYS(32); else INK_MIDKEYS(64);
 #undef INK_MIDKEYS
   return ink_launch_status();
+}
+
+extern "C" int ink_attn_midkeys(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                int64_t ldv, int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads,
+                                int32_t head_dim, float scale, const uint8_t* blocked, void* O, int64_t ldo,
+                                void* stream) {
+  return midkeys_launch(Q, ldq, K, ldk, V, ldv, B, n_q, n_k, n_heads, head_dim, scale, blocked, 0, nullptr, O, ldo,
+                        stream);
+}
+
+extern "C" int ink_attn_midkeys_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                       int64_t ldv, int32_t B, int32_t n_q, int32_t n_k, int32_t n_heads,
+                                       int32_t head_dim, float scale, const uint8_t* blocked,
+                                       int64_t blocked_batch_stride, const int32_t* k_len, void* O, int64_t ldo,
+                                       void* stream) {
+  INK_CHECK_ARG(blocked_batch_stride >= 0 && (blocked || blocked_batch_stride == 0) && ink_aligned<4>(k_len));
+  return midkeys_launch(Q, ldq, K, ldk, V, ldv, B, n_q, n_k, n_heads, head_dim, scale, blocked, blocked_batch_stride,
+                        k_len, O, ldo, stream);
 }
 
 extern "C" int ink_attn_fewq(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,

@@ -28,7 +28,8 @@
 //   wide_merge     combines the chunks: out_l = sum_c partial_c e^(m_c - M) / sum_c sumexp_c e^(m_c - M), M = max m_c.
 // Weights enter the value MFMAs as f16(w * 2^14) with w = exp(score - max) <= 1 and the normaliser is the sum of those
 // SAME rounded numbers, so the weights of an output are an exact convex combination and only weights below 2^-28 of
-// the largest fall below f16's smallest normal.  No atomics: every output element has one writer and a fixed
+// the largest fall below f16's smallest normal.  ink_biattn_wide_varlen gives every image its own token count (a
+// device array t_len; KL / out_l rows at stride Tmax): the kernels are the same text, see image_tokens.  No atomics: every output element has one writer and a fixed
 // summation order, so the results of image b are bitwise independent of B and identical run to run.
 //
 // Workspace (ink_biattn_wide_workspace, in floats), Tp as above, NG = ceil(S/128), NC = ceil(S/1024):
@@ -71,16 +72,26 @@ __device__ __forceinline__ f32x16 score_tile(const f16* __restrict__ Qh, const f
   return acc;
 }
 
-// values_l of every head, transposed and padded: VLt[b][h][d][t] = KL[b*T + t][E + 256 h + d], zero for t >= T
+// The token count of image b.  t_len == nullptr: every image has the launch's T (ink_biattn_wide).  Otherwise
+// (ink_biattn_wide_varlen) T is the row stride Tmax of KL / out_l and image b has t_len[b] tokens, clamped into 1..T
+// here so that a bad device value cannot index out of range.  Every kernel below derives its own padded count
+// Tpb = 32 ceil(Tb / 32) from it - an image's arithmetic is that of a uniform launch at T = Tb - while the workspace
+// strides stay at the launch-wide Tp.
+__device__ __forceinline__ int image_tokens(const int32_t* __restrict__ t_len, int b, int T) {
+  return t_len ? min(max(t_len[b], 1), T) : T;
+}
+
+// values_l of every head, transposed and padded: VLt[b][h][d][t] = KL[b*T + t][E + 256 h + d], zero for t >= Tb (a pad
+// row of KL is never read)
 __global__ __launch_bounds__(256) void wide_prep_kernel(const f16* __restrict__ KL, int T, int Tp, int64_t total,
-                                                        f16* __restrict__ VLt) {
+                                                        const int32_t* __restrict__ t_len, f16* __restrict__ VLt) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int t = (int)(i % Tp);
   const int64_t r = i / Tp;                                 // (b * 4 + h) * 256 + d
   const int d = (int)(r % BW_HD), h = (int)((r / BW_HD) % BW_H);
   const int64_t b = r / (BW_HD * BW_H);
-  VLt[i] = t < T ? KL[(b * T + t) * BW_LD + BW_E + h * BW_HD + d] : (f16)0.f;
+  VLt[i] = t < image_tokens(t_len, (int)b, T) ? KL[(b * T + t) * BW_LD + BW_E + h * BW_HD + d] : (f16)0.f;
 }
 
 constexpr int BW_SS = 256 + 4;         // f32 row stride of the score tile (floats)
@@ -88,38 +99,39 @@ constexpr int BW_ES = 256 + 8;         // f16 row stride of the weight tile (hal
 
 __global__ __launch_bounds__(BW_THREADS) void wide_image_kernel(const f16* __restrict__ QV, const f16* __restrict__ KL,
                                                                 const f16* __restrict__ VLt, int S, int T, int Tp,
-                                                                float scale, float* __restrict__ gmax,
+                                                                const int32_t* __restrict__ t_len, float scale,
+                                                                float* __restrict__ gmax,
                                                                 f16* __restrict__ out_v) {
   __shared__ __attribute__((aligned(16))) float ssc[BW_TILE * BW_SS];
   __shared__ __attribute__((aligned(16))) f16 e16[BW_TILE * BW_ES];
   __shared__ float inv[BW_TILE];
   const int g = blockIdx.x, h = blockIdx.y, b = blockIdx.z, NG = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const int NT = Tp / 32;
+  const int Tb = image_tokens(t_len, b, T), Tpb = (Tb + 31) / 32 * 32, NT = Tpb / 32;
   const f16* Qh = QV + (int64_t)b * S * BW_LD + h * BW_HD;
   const f16* Kh = KL + (int64_t)b * T * BW_LD + h * BW_HD;
   const f16* vl = VLt + (((int64_t)b * BW_H + h) * BW_HD + w * 32 + r) * Tp + 8 * hh;
-  float cm = -INFINITY;                                     // thread tid < Tp: running max of text column tid
+  float cm = -INFINITY;                                     // thread tid < Tpb: running max of text column tid
   for (int tile = 0; tile < BW_GROUP / BW_TILE; ++tile) {
     const int s0 = g * BW_GROUP + tile * BW_TILE;
     if (s0 >= S) break;                                     // uniform over the workgroup
     const int nrow = min(BW_TILE, S - s0);
     if (w < NT) {
-      const f32x16 sc = score_tile(Qh, Kh, S, T, s0, w, scale, lane);
+      const f32x16 sc = score_tile(Qh, Kh, S, Tb, s0, w, scale, lane);
 #pragma unroll
       for (int i = 0; i < 16; ++i) ssc[acc_row(i, hh) * BW_SS + w * 32 + r] = sc[i];
     }
     __syncthreads();
-    if (tid < Tp)
+    if (tid < Tpb)
       for (int row = 0; row < nrow; ++row) cm = fmaxf(cm, ssc[row * BW_SS + tid]);
     {   // row softmax: 16 consecutive lanes per row
       const int row = tid >> 4, sub = tid & 15;
       float m = -INFINITY;
-      for (int c = sub; c < Tp; c += 16) m = fmaxf(m, ssc[row * BW_SS + c]);
+      for (int c = sub; c < Tpb; c += 16) m = fmaxf(m, ssc[row * BW_SS + c]);
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
       float sum = 0.f;
-      for (int c = sub; c < Tp; c += 16) {
+      for (int c = sub; c < Tpb; c += 16) {
         const f16 e = (f16)(expf(ssc[row * BW_SS + c] - m) * BW_PSCALE);   // pad column: exp(-inf) = 0
         e16[row * BW_ES + c] = e;
         sum += (float)e;
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(BW_THREADS) void wide_image_kernel(const f16* __res
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int ks = 0; ks < Tp / 16; ++ks)
+    for (int ks = 0; ks < Tpb / 16; ++ks)
       acc = mfma32(*(const f16x8*)(e16 + r * BW_ES + 16 * ks + 8 * hh), *(const f16x8*)(vl + 16 * ks), acc);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -142,25 +154,26 @@ __global__ __launch_bounds__(BW_THREADS) void wide_image_kernel(const f16* __res
     // the next tile's ssc writes wait behind the barrier above (every softmax read is done), its e16 / inv writes
     // behind its own first barrier (every MFMA read and store of this tile is done)
   }
-  if (tid < Tp) gmax[(((int64_t)b * BW_H + h) * NG + g) * Tp + tid] = cm;
+  if (tid < Tpb) gmax[(((int64_t)b * BW_H + h) * NG + g) * Tp + tid] = cm;
 }
 
 constexpr int BW_VS = 40;              // f16 row stride of the transposed values_v tile (halves; 80 B, 16-byte aligned)
 
 __global__ __launch_bounds__(BW_THREADS) void wide_text_kernel(const f16* __restrict__ QV, const f16* __restrict__ KL,
                                                                const float* __restrict__ gmax, int S, int T, int Tp,
-                                                               int NG, float scale, float* __restrict__ tstat,
+                                                               const int32_t* __restrict__ t_len, int NG,
+                                                               float scale, float* __restrict__ tstat,
                                                                float* __restrict__ partial) {
   __shared__ __attribute__((aligned(16))) f16 vvt[BW_HD * BW_VS];   // [value dim][image row, in accumulator k order]
   __shared__ float cmx[256];
   const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, NC = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const int NT = Tp / 32;
+  const int Tb = image_tokens(t_len, b, T), Tpb = (Tb + 31) / 32 * 32, NT = Tpb / 32;
   const f16* Qh = QV + (int64_t)b * S * BW_LD + h * BW_HD;
   const f16* Kh = KL + (int64_t)b * T * BW_LD + h * BW_HD;
   const f16* VVh = QV + (int64_t)b * S * BW_LD + BW_E + h * BW_HD;
   const int s_begin = c * BW_CHUNK, s_end = min(S, s_begin + BW_CHUNK);
-  if (tid < Tp) {
+  if (tid < Tpb) {
     const int g0 = c * (BW_CHUNK / BW_GROUP), g1 = min(NG, g0 + BW_CHUNK / BW_GROUP);
     float m = -INFINITY;
     for (int g = g0; g < g1; ++g) m = fmaxf(m, gmax[(((int64_t)b * BW_H + h) * NG + g) * Tp + tid]);
@@ -168,7 +181,7 @@ __global__ __launch_bounds__(BW_THREADS) void wide_text_kernel(const f16* __rest
   }
   __syncthreads();
   const int t = w * 32 + r;                                 // this lane's text column (w < NT)
-  const bool live = w < NT && t < T;
+  const bool live = w < NT && t < Tb;
   const float mycm = live ? cmx[t] : 0.f;
   f32x16 acc[8];
 #pragma unroll
@@ -189,7 +202,7 @@ __global__ __launch_bounds__(BW_THREADS) void wide_text_kernel(const f16* __rest
     }
     __syncthreads();
     if (w < NT) {
-      const f32x16 sc = score_tile(Qh, Kh, S, T, s0, w, scale, lane);
+      const f32x16 sc = score_tile(Qh, Kh, S, Tb, s0, w, scale, lane);
       f16x8 p[2];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -220,11 +233,16 @@ __global__ __launch_bounds__(BW_THREADS) void wide_text_kernel(const f16* __rest
   }
 }
 
-// out_l[b*T + t, 256 h + d] from the chunks' (m_c, sum-exp, partial): grid (T, 4, B), thread = value dim d
+// out_l[b*T + t, 256 h + d] from the chunks' (m_c, sum-exp, partial): grid (T, 4, B), thread = value dim d; the rows
+// t >= Tb of an image with fewer tokens than the launch's T are written as zeros
 __global__ __launch_bounds__(BW_HD) void wide_merge_kernel(const float* __restrict__ tstat,
                                                            const float* __restrict__ partial, int T, int Tp, int NC,
-                                                           f16* __restrict__ out_l) {
+                                                           const int32_t* __restrict__ t_len, f16* __restrict__ out_l) {
   const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
+  if (t >= image_tokens(t_len, b, T)) {                     // uniform over the workgroup
+    out_l[((int64_t)b * T + t) * BW_E + h * BW_HD + d] = (f16)0.f;
+    return;
+  }
   const int64_t base = ((int64_t)b * BW_H + h) * NC;
   float M = -INFINITY;
   for (int c = 0; c < NC; ++c) M = fmaxf(M, tstat[((base + c) * Tp + t) * 2]);
@@ -261,23 +279,38 @@ extern "C" int ink_biattn_wide_workspace(int32_t B, int32_t S, int32_t T, int64_
   return INK_OK;
 }
 
-extern "C" int ink_biattn_wide(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, int32_t E,
-                               float scale, float* ws, void* out_v_f16, void* out_l_f16, void* stream) {
-  INK_CHECK_ARG(QV_f16 && KL_f16 && ws && out_v_f16 && out_l_f16);
-  INK_CHECK_ARG(B > 0 && B <= 65535 && S > 0 && S <= 32768 && T >= 1 && T <= 256 && E == BW_E);
-  INK_CHECK_ARG(ink_aligned<16>(QV_f16, KL_f16, ws, out_v_f16, out_l_f16));   // 16-byte fragment loads
+// the four launches of both entry points: t_len == nullptr is the uniform form
+static int wide_launch(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, const int32_t* t_len,
+                       float scale, float* ws, void* out_v_f16, void* out_l_f16, void* stream) {
   const WideWs o = wide_ws(B, S, T);
   hipStream_t s = (hipStream_t)stream;
   f16* vlt = (f16*)(ws + o.vlt);
   const int64_t nprep = (int64_t)B * BW_H * BW_HD * o.Tp;
   hipLaunchKernelGGL(wide_prep_kernel, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, s, (const f16*)KL_f16, T,
-                     o.Tp, nprep, vlt);
+                     o.Tp, nprep, t_len, vlt);
   hipLaunchKernelGGL(wide_image_kernel, dim3(o.NG, BW_H, B), dim3(BW_THREADS), 0, s, (const f16*)QV_f16,
-                     (const f16*)KL_f16, (const f16*)vlt, S, T, o.Tp, scale, ws + o.gmax, (f16*)out_v_f16);
+                     (const f16*)KL_f16, (const f16*)vlt, S, T, o.Tp, t_len, scale, ws + o.gmax, (f16*)out_v_f16);
   hipLaunchKernelGGL(wide_text_kernel, dim3(o.NC, BW_H, B), dim3(BW_THREADS), 0, s, (const f16*)QV_f16,
-                     (const f16*)KL_f16, (const float*)(ws + o.gmax), S, T, o.Tp, o.NG, scale, ws + o.tstat,
+                     (const f16*)KL_f16, (const float*)(ws + o.gmax), S, T, o.Tp, t_len, o.NG, scale, ws + o.tstat,
                      ws + o.partial);
   hipLaunchKernelGGL(wide_merge_kernel, dim3(T, BW_H, B), dim3(BW_HD), 0, s, (const float*)(ws + o.tstat),
-                     (const float*)(ws + o.partial), T, o.Tp, o.NC, (f16*)out_l_f16);
+                     (const float*)(ws + o.partial), T, o.Tp, o.NC, t_len, (f16*)out_l_f16);
   return ink_launch_status();
+}
+
+extern "C" int ink_biattn_wide(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t T, int32_t E,
+                               float scale, float* ws, void* out_v_f16, void* out_l_f16, void* stream) {
+  INK_CHECK_ARG(QV_f16 && KL_f16 && ws && out_v_f16 && out_l_f16);
+  INK_CHECK_ARG(B > 0 && B <= 65535 && S > 0 && S <= 32768 && T >= 1 && T <= 256 && E == BW_E);
+  INK_CHECK_ARG(ink_aligned<16>(QV_f16, KL_f16, ws, out_v_f16, out_l_f16));   // 16-byte fragment loads
+  return wide_launch(QV_f16, KL_f16, B, S, T, nullptr, scale, ws, out_v_f16, out_l_f16, stream);
+}
+
+extern "C" int ink_biattn_wide_varlen(const void* QV_f16, const void* KL_f16, int32_t B, int32_t S, int32_t Tmax,
+                                      const int32_t* t_len, int32_t E, float scale, float* ws, void* out_v_f16,
+                                      void* out_l_f16, void* stream) {
+  INK_CHECK_ARG(QV_f16 && KL_f16 && t_len && ws && out_v_f16 && out_l_f16);
+  INK_CHECK_ARG(B > 0 && B <= 65535 && S > 0 && S <= 32768 && Tmax >= 1 && Tmax <= 256 && E == BW_E);
+  INK_CHECK_ARG(ink_aligned<16>(QV_f16, KL_f16, ws, out_v_f16, out_l_f16) && ink_aligned<4>(t_len));
+  return wide_launch(QV_f16, KL_f16, B, S, Tmax, t_len, scale, ws, out_v_f16, out_l_f16, stream);
 }

@@ -17,14 +17,15 @@ MI355X-first structure (not a translation of the nn.Module tree):
     caption of 5..256 tokens runs the three products on MFMA with no score matrix at all, csrc/biattn_wide.hip);
   * everything that does not depend on the pixels (sine position embeddings, reference points,
     anchors, masks, maps, the BERT text features of the caption - "object." by default) is folded at load, or once
-    per caption (set_caption; predict returns a phrase per box).
+    per caption (set_caption; predict returns a phrase per box); a batch may carry one caption per image
+    (set_captions: per-image token counts and text padding masks, csrc/biattn_wide.hip / attn_few.hip varlen forms).
 Equal-sized images per batch (NestedTensor masks all False) — what InkLayer feeds.
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, replace
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -381,6 +382,17 @@ def clean_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return sd
 
 
+class _TextBatch(NamedTuple):
+    """The text side of one per-image-caption forward (GDinoEngine.set_captions), rows of the images in that launch."""
+    text0: torch.Tensor      # f32 [B*Tmax, 256], pad rows zero
+    t_len: torch.Tensor      # int32 [B] on the device
+    blocked: torch.Tensor    # u8 [B, Tmax, Tmax]
+    pos_text: torch.Tensor   # f32 [B*Tmax, 256]
+    bias: torch.Tensor       # f32 [B, Tc]: -inf at t >= T_b
+    Tmax: int
+    Tc: int                  # 4 ceil(Tmax / 4): the columns of ContrastiveEmbed's GEMM
+
+
 class GDinoEngine:
     fuse_ffn = True          # encoder FFN + norm2 as one kernel (csrc/ffn_fused.hip); False: two GEMMs + LayerNorm
     fuse_ffn_pre = True      # ... starting at the deformable attention's output projection (out_proj + norm1 inside)
@@ -524,9 +536,10 @@ class GDinoEngine:
     def set_text(self, encoded_text: Optional[torch.Tensor], token_ids: Sequence[int]) -> None:
         """encoded_text = feat_map(BERT(caption)) [T, 256] (groundingdino.py:277-279), a constant of the caption.
         T <= cfg.max_text_len (256); a longer id list is truncated to that first, as groundingdino.py:259-266 does (a
-        phrase the cut runs through is left without its closing separator, so its tokens see only themselves).  ONE
-        caption per engine state, shared by every image of a batch: per-image captions with padding masks are out of
-        scope.  Plans stay (they do not depend on the text); captured graphs are dropped."""
+        phrase the cut runs through is left without its closing separator, so its tokens see only themselves).  This
+        is the SHARED-caption form: one caption for every image of a batch, the folded T <= 4 path and graphs
+        included.  A batch with one caption per image is set_captions' per-image form; set_text / set_caption leave
+        it and clear its state.  Plans stay (they do not depend on the text); captured graphs are dropped."""
         if encoded_text is None:
             raise ValueError("encoded_text [T,256] is required: fold BERT + feat_map once at load "
                              "(inklayer_amd.text_branch) or pass precomputed features")
@@ -537,6 +550,7 @@ class GDinoEngine:
         assert T >= 1
         self._graphs.clear()                           # captured forwards hold the old text tensors
         self._seen.clear()
+        self.captions = self.t_lens = self.t_len = self.Tmax = self.text_position_ids = None   # per-image form off
         self.T = T
         self.token_ids = tuple(int(t) for t in token_ids)
         # dispatch on T alone: _enc_layer folds <= 4 tokens through the fusion layer and runs the general kernel
@@ -566,12 +580,20 @@ class GDinoEngine:
         Its text features are encoded_text [T, 256] where given, else feat_map(BERT(ids)) folded on the host from the
         checkpoint's bert.* / feat_map.* tensors (text_branch.encode_caption_from_checkpoint; sd is remembered from
         the first call that passes one) - once per caption: the last `caption_cache_size` captions are kept.  BERT
-        is host-side torch and not on the hot path.  One caption per engine state, see set_text."""
+        is host-side torch and not on the hot path.  The shared-caption form, see set_text; set_captions takes one
+        caption per image."""
         ids = tuple(int(t) for t in token_ids)[:self.cfg.max_text_len]
+        self._take_text_weights(sd)
+        self.set_text(self._caption_features(ids, encoded_text), ids)
+
+    def _take_text_weights(self, sd: Optional[Dict[str, torch.Tensor]]) -> None:
         if sd is not None:
             sd = clean_state_dict(sd)
             self.text_weights = {k: v for k, v in sd.items() if k.startswith(("bert.", "feat_map."))}
             self._captions.clear()                          # features folded from another checkpoint
+
+    def _caption_features(self, ids: Tuple[int, ...], encoded_text: Optional[torch.Tensor]) -> torch.Tensor:
+        """[len(ids), 256] text features of an (already truncated) caption: the given ones, the cache's, or BERT's."""
         if encoded_text is None:
             encoded_text = self._captions.get(ids)
         if encoded_text is None:
@@ -580,7 +602,58 @@ class GDinoEngine:
                                  "and feat_map.* tensors")
             from .text_branch import encode_caption_from_checkpoint
             encoded_text = encode_caption_from_checkpoint(self.text_weights, ids)
-        self.set_text(encoded_text[:len(ids)], ids)
+        return encoded_text[:len(ids)]
+
+    def set_captions(self, token_id_lists: Sequence[Sequence[int]], sd: Optional[Dict[str, torch.Tensor]] = None,
+                     encoded_texts: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+        """One caption PER IMAGE of the next batch (GroundingDINO.forward with a list of captions,
+        groundingdino.py:243-279): token_id_lists[i] belongs to image i of the next forward / predict, each truncated
+        to cfg.max_text_len; features from encoded_texts[i], the caption cache or BERT folded on the host, as
+        set_caption finds them.  Equal captions are the shared form: set_caption and its paths, bit for bit.
+        Otherwise the engine enters the per-image form, the reference's padding="longest" batch with Tmax = max T_b:
+          text0 [B*Tmax, 256] (pad rows zero), t_len int32 [B] on the device, text_blocked u8 [B, Tmax, Tmax] (each
+          caption's block-diagonal mask in the corner; pad rows and columns blocked except the diagonal, which is what
+          bertwarper.py's generate_masks_with_special_tokens_and_transfer_map gives for pad ids - the key count removes
+          the pad keys anyway), pos_text [B*Tmax, 256] (position id 0 at pads; the ids are text_position_ids),
+          logit_bias [B, Tc] (-inf at t >= T_b; Tc = 4 ceil(Tmax / 4)).
+        A forward in this form runs eager on ops.biattn_wide_varlen / ops.attn_midkeys_varlen: every image pays for
+        its own token count, and its results are those of its caption alone (text_token_mask of the reference:
+        fuse_modules.py:214-218, transformer.py:903-909, utils.py:259-262)."""
+        caps = [tuple(int(t) for t in ids)[:self.cfg.max_text_len] for ids in token_id_lists]
+        if not caps or any(len(c) < 1 for c in caps):
+            raise ValueError("set_captions needs at least one caption, each of at least one token id")
+        if encoded_texts is not None and len(encoded_texts) != len(caps):
+            raise ValueError("one encoded_text (or None) per caption")
+        feats_in = list(encoded_texts) if encoded_texts is not None else [None] * len(caps)
+        if len(set(caps)) == 1:
+            return self.set_caption(caps[0], sd=sd, encoded_text=feats_in[0])
+        self._take_text_weights(sd)
+        feats = [self._caption_features(ids, f).detach().to("cpu", F32) for ids, f in zip(caps, feats_in)]
+        for ids, f in zip(caps, feats):
+            assert f.shape[0] == len(ids), "one feature row per token id"
+            self._captions.put(ids, f)
+        B, Tmax = len(caps), max(len(c) for c in caps)
+        self._graphs.clear()                           # captured forwards hold the old text tensors
+        self._seen.clear()
+        self.T = self.token_ids = self._text_attn = None     # the shared form's state: a use of it is an error
+        self.captions, self.t_lens, self.Tmax, self.Tc = tuple(caps), tuple(len(c) for c in caps), Tmax, -(-Tmax // 4) * 4
+        text0 = torch.zeros(B, Tmax, 256, dtype=F32)
+        blocked = ~torch.eye(Tmax, dtype=torch.bool).repeat(B, 1, 1)
+        pid = torch.zeros(B, Tmax, dtype=torch.long)
+        bias = torch.zeros(B, self.Tc, dtype=F32)
+        for b, (ids, f) in enumerate(zip(caps, feats)):
+            n = len(ids)
+            sm, p = text_masks_and_position_ids(ids)
+            text0[b, :n], blocked[b, :n, :n], pid[b, :n] = f, ~sm, p
+            bias[b, n:] = float("-inf")
+        self.text_position_ids = pid
+        self.text0 = text0.view(B * Tmax, 256).to(self.dev).contiguous()
+        self.t_len = torch.tensor(self.t_lens, dtype=I32).to(self.dev)
+        self.text_blocked = blocked.to(torch.uint8).to(self.dev).contiguous()
+        dim_t = torch.arange(256, dtype=torch.float32)
+        dim_t = 10000.0 ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / 256)
+        self.pos_text = _interleaved_sincos(pid.view(-1).float()[:, None] * (2 * math.pi) / dim_t).to(self.dev).contiguous()
+        self.logit_bias = bias.to(self.dev)
 
     def predict(self, images_u8: Sequence[torch.Tensor], box_threshold: float, text_threshold: float,
                 remove_combined: bool = False):
@@ -589,13 +662,15 @@ class GDinoEngine:
         forms them (strings with self.tokenizer set, id tuples without)."""
         logits, boxes = self.forward(images_u8)
         both = torch.cat([logits, boxes], dim=-1).cpu()       # single D2H copy
-        T, res = self.T, []
+        TL, res = logits.shape[-1], []                        # T, or Tmax in the per-image form
         for b in range(both.shape[0]):
+            # the per-image form slices image b's own T_b columns and forms the phrases from its own ids
+            T, ids = (self.T, self.token_ids) if self.captions is None else (self.t_lens[b], self.captions[b])
             prob = both[b, :, :T].contiguous().sigmoid()      # dense [nq, T], as the reference's `.cpu().sigmoid()[0]`
             keep = prob.max(dim=1)[0] > box_threshold
             kept = prob[keep]
-            phrases = phrases_from_probs(kept, self.token_ids, text_threshold, remove_combined, self.tokenizer)
-            res.append((both[b, keep, T:], kept.max(dim=1)[0] if len(kept) else kept.new_zeros(0), phrases))
+            phrases = phrases_from_probs(kept, ids, text_threshold, remove_combined, self.tokenizer)
+            res.append((both[b, keep, TL:], kept.max(dim=1)[0] if len(kept) else kept.new_zeros(0), phrases))
         return res
 
     # ------------------------------------------------------------------ HIP graphs (latency mode)
@@ -725,7 +800,8 @@ class GDinoEngine:
     def encoder(self, src: torch.Tensor, pl: _Plan, B: int):
         """TransformerEncoder.forward (transformer.py:481-595): fusion -> text layer -> deformable layer, x6."""
         S = pl.S
-        text = self.text0.repeat(B, 1)                        # [B*T, 256] (plumbing copy)
+        tb = self._tb
+        text = self.text0.repeat(B, 1) if tb is None else tb.text0.clone()    # [B*T, 256] (plumbing copy)
         s16 = torch.empty((B * S, 256), device=self.dev, dtype=F16)
         s16p = torch.empty((B * S, 256), device=self.dev, dtype=F16)
         for i in range(self.cfg.enc_layers):
@@ -737,14 +813,14 @@ class GDinoEngine:
         """Encoder layer i: fusion, text enhancer, deformable layer on src [B*S, 256] f32 (updated in place on the
         product path) and text [B*T, 256] f32; s16 / s16p are the [B*S, 256] f16 operand buffers every layer re-uses.
         Returns (src, text)."""
-        w, dev, T, S = self.w, self.dev, self.T, pl.S
+        w, dev, T, S, tb = self.w, self.dev, self.T, pl.S, self._tb
         d = f"e{i}"
         have16 = False
         # --- BiAttentionBlock (fuse_modules.py:286-295): residual from the NORMALISED v / l
         ln32 = torch.empty_like(text)
         l16 = torch.empty(text.shape, device=dev, dtype=F16)
         ops.layernorm_rows(text, w[d + ".fu.lnl.w"], w[d + ".fu.lnl.b"], 1e-5, out=ln32, out2=l16)
-        if self.fold_fusion and T <= 4:
+        if tb is None and self.fold_fusion and T <= 4:
             # the caption's <= 4 tokens folded through the fusion layer (csrc/fusion_fold.hip): no per-token
             # 256 -> 2048 projection, no 1024 -> 256 image output projection, f32 throughout
             kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"])
@@ -758,14 +834,22 @@ class GDinoEngine:
             ops.layernorm_rows(src, w[d + ".fu.lnv.w"], w[d + ".fu.lnv.b"], 1e-5, out=vn, out2=s16)
             qv = ops.gemm(s16, w[d + ".fu.qv.w"], w[d + ".fu.qv.b"], out_dtype=F16)
             kl = ops.gemm(l16, w[d + ".fu.kl.w"], w[d + ".fu.kl.b"], out_dtype=F16)
-            ov, ol = ops.biattn_wide(qv, kl, B, S, T, 256 ** -0.5)
+            if tb is None:
+                ov, ol = ops.biattn_wide(qv, kl, B, S, T, 256 ** -0.5)
+            else:   # per-image token counts: pad rows of kl are never read, pad rows of ol come back as zeros
+                ov, ol = ops.biattn_wide_varlen(qv, kl, B, S, tb.Tmax, tb.t_len, 256 ** -0.5)
             src = ops.gemm(ov, w[d + ".fu.outv.w"], w[d + ".fu.outv.b"], col_scale=w[d + ".fu.gv"], residual=vn, out=vn)
         text = ops.gemm(ol, w[d + ".fu.outl.w"], w[d + ".fu.outl.b"], col_scale=w[d + ".fu.gl"], residual=ln32)
         # --- text enhancer (transformer_vanilla.py:101-123), 4 heads x 64, block-diagonal mask
-        qk = ops.gemm(ops.add_cvt_f16(text, self.pos_text), w[d + ".txt.qk.w"], w[d + ".txt.qk.b"], out_dtype=F16)
+        qk = ops.gemm(ops.add_cvt_f16(text, self.pos_text if tb is None else tb.pos_text), w[d + ".txt.qk.w"],
+                      w[d + ".txt.qk.b"], out_dtype=F16)
         vv = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.v.w"], w[d + ".txt.v.b"], out_dtype=F16)
-        a = self._text_attn(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
-                            blocked=self.text_blocked)
+        if tb is None:
+            a = self._text_attn(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
+                                blocked=self.text_blocked)
+        else:       # each image's own mask and key count; a pad row has no key and gives zeros
+            a = ops.attn_midkeys_varlen(qk[:, :256], qk[:, 256:], vv, B=B, n_heads=4, head_dim=64, scale=64 ** -0.5,
+                                        blocked=tb.blocked, k_len=tb.t_len)
         text = ops.layernorm_rows(ops.gemm(a, w[d + ".txt.out.w"], w[d + ".txt.out.b"], residual=text),
                                   w[d + ".txt.norm1.w"], w[d + ".txt.norm1.b"], 1e-5, out_dtype=F32)
         ff = ops.gemm(ops.add_cvt_f16(text), w[d + ".txt.lin1.w"], w[d + ".txt.lin1.b"], act="relu", out_dtype=F16)
@@ -801,20 +885,22 @@ class GDinoEngine:
     def decoder(self, memory: torch.Tensor, text: torch.Tensor, pl: _Plan, B: int, stages: Optional[dict] = None):
         """Two-stage selection + TransformerDecoder + heads (transformer.py:284-327, 665-735;
         groundingdino.py:331-349).  Returns (logits [B,nq,T], boxes [B,nq,4]) f32 on the GPU."""
-        cfg, w, dev, T, S, nq = self.cfg, self.w, self.dev, self.T, pl.S, self.cfg.num_queries
+        cfg, w, dev, S, nq, tb = self.cfg, self.w, self.dev, pl.S, self.cfg.num_queries, self._tb
+        T = self.T if tb is None else tb.Tmax                # per-image form: Tmax columns, bias row b = -inf at t >= T_b
         om16 = ops.gather_rows(memory, pl.valid_map, B, S, x_batch_rows=S, idx_batch_stride=0)
         om = ops.gemm(om16, w["enc_output.w"], w["enc_output.b"])
         omn16 = torch.empty((B * S, 256), device=dev, dtype=F16)
         omn = ops.layernorm_rows(om, w["enc_output_norm.w"], w["enc_output_norm.b"], 1e-5, out=om, out2=omn16)
         text16 = ops.add_cvt_f16(text)
-        Tc, tw16, tbias = self.Tc, text16, self.logit_bias
+        Tc, tw16 = (self.Tc if tb is None else tb.Tc), text16
+        tbias = [self.logit_bias] * B if tb is None else list(tb.bias.unbind(0))
         if Tc != T:          # zero text rows with bias -inf (set_text): a pad column is never a row's maximum
             tw16 = torch.zeros((B, Tc, 256), device=dev, dtype=F16)
             tw16[:, :T] = text16.view(B, T, 256)
             tw16 = tw16.view(B * Tc, 256)
         logits = torch.empty((B, S, Tc), device=dev, dtype=F32)
         for b in range(B):   # ContrastiveEmbed: per-image "weights" = that image's text features
-            ops.gemm(omn16[b * S:(b + 1) * S], tw16[b * Tc:(b + 1) * Tc], tbias, out=logits[b])
+            ops.gemm(omn16[b * S:(b + 1) * S], tw16[b * Tc:(b + 1) * Tc], tbias[b], out=logits[b])
         idx = ops.topk_rowmax(logits, nq)
         if stages is not None:
             stages["topk_logits"] = logits if Tc == T else logits[:, :, :T]
@@ -846,7 +932,7 @@ class GDinoEngine:
         boxes = ops.box_refine(self._mlp3("box", hs16), ref).view(B, nq, 4)
         out_logits = torch.empty((B, nq, Tc), device=dev, dtype=F32)
         for b in range(B):
-            ops.gemm(hs16[b * nq:(b + 1) * nq], tw16[b * Tc:(b + 1) * Tc], tbias, out=out_logits[b])
+            ops.gemm(hs16[b * nq:(b + 1) * nq], tw16[b * Tc:(b + 1) * Tc], tbias[b], out=out_logits[b])
         return (out_logits if Tc == T else out_logits[:, :, :T]), boxes
 
     def _dec_layer(self, i: int, output: torch.Tensor, ref: torch.Tensor, mem16: torch.Tensor, text16: torch.Tensor,
@@ -869,7 +955,11 @@ class GDinoEngine:
         # text cross-attention (keys/values = the T text tokens)
         q = ops.gemm(ops.add_cvt_f16(output, qpos), w[d + ".ca.q.w"], w[d + ".ca.q.b"], out_dtype=F16)
         kv = ops.gemm(text16, w[d + ".ca.kv.w"], w[d + ".ca.kv.b"], out_dtype=F16)
-        a = self._text_attn(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
+        if self._tb is None:
+            a = self._text_attn(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5)
+        else:       # key_padding_mask (transformer.py:903-909): image b's keys end at its own token count
+            a = ops.attn_midkeys_varlen(q, kv[:, :256], kv[:, 256:], B=B, n_heads=8, head_dim=32, scale=32 ** -0.5,
+                                        k_len=self._tb.t_len)
         output = ops.layernorm_rows(ops.gemm(a, w[d + ".ca.out.w"], w[d + ".ca.out.b"], residual=output),
                                     w[d + ".canorm.w"], w[d + ".canorm.b"], 1e-5, out_dtype=F32)
         # deformable cross-attention into the encoder memory (4-d reference boxes)
@@ -889,6 +979,8 @@ class GDinoEngine:
         Images of different sizes are run as separate equal-size groups (the reference pads a NestedTensor
         instead; it only ever sees one image per call, GD/util/inference.py:67)."""
         B = len(images_u8)
+        if self.captions is not None:
+            return self._forward_captions(images_u8, stages)
         sizes = [tuple(im.shape[:2]) for im in images_u8]
         if len(set(sizes)) > 1:
             assert stages is None
@@ -905,6 +997,44 @@ class GDinoEngine:
         if allow_graph and stages is None and 0 < B <= self.graph_max_batch:
             return self._forward_graphed(images_u8, h, w_)
         return self._forward_eager(images_u8, stages)
+
+    _tb: Optional["_TextBatch"] = None     # the per-image text state of the forward in flight (None: shared caption)
+
+    def _forward_captions(self, images_u8: Sequence[torch.Tensor], stages: Optional[dict] = None):
+        """forward in the per-image form (set_captions): caption i belongs to image i.  Eager, no graph.  Images of
+        different sizes run as size groups, each with its own images' captions.  -> (logits [B, nq, Tmax] with -inf in
+        each image's pad columns, as the reference returns -inf up to max_text_len; boxes [B, nq, 4])."""
+        B = len(images_u8)
+        if B != len(self.captions):
+            raise ValueError(f"{B} images for {len(self.captions)} captions: set_captions takes one caption per image")
+        sizes = [tuple(im.shape[:2]) for im in images_u8]
+        groups = [[i for i, s_ in enumerate(sizes) if s_ == sz] for sz in dict.fromkeys(sizes)]
+        Tmax = self.Tmax
+        if len(groups) == 1:
+            self._tb = _TextBatch(self.text0, self.t_len, self.text_blocked, self.pos_text, self.logit_bias, Tmax, self.Tc)
+            try:
+                return self._forward_eager(images_u8, stages)
+            finally:
+                self._tb = None
+        assert stages is None
+        logits = torch.full((B, self.cfg.num_queries, Tmax), float("-inf"), device=self.dev, dtype=F32)
+        boxes = torch.empty((B, self.cfg.num_queries, 4), device=self.dev, dtype=F32)
+        for idx in groups:
+            # the group's own longest caption: exactly the launches set_captions + forward of these images alone make
+            ii = torch.tensor(idx, device=self.dev)
+            Tg = max(self.t_lens[i] for i in idx)
+            Tcg = -(-Tg // 4) * 4
+            self._tb = _TextBatch(self.text0.view(B, Tmax, 256)[ii, :Tg].reshape(-1, 256), self.t_len[ii].contiguous(),
+                                  self.text_blocked[ii, :Tg, :Tg].contiguous(),
+                                  self.pos_text.view(B, Tmax, 256)[ii, :Tg].reshape(-1, 256),
+                                  self.logit_bias[ii, :Tcg].contiguous(), Tg, Tcg)
+            try:
+                lg, bx = self._forward_eager([images_u8[i] for i in idx])
+            finally:
+                self._tb = None
+            logits[ii, :, :Tg] = lg
+            boxes[ii] = bx
+        return logits, boxes
 
     def _forward_eager(self, images_u8: Sequence[torch.Tensor], stages: Optional[dict] = None):
         B = len(images_u8)
@@ -928,8 +1058,9 @@ class GDinoEngine:
         return self.postprocess(both, top_n)
 
     def postprocess(self, both: torch.Tensor, top_n: Optional[int] = None):
-        """Host half of predict(): `both` = cat(logits, boxes) [B, nq, T+4] on the CPU."""
-        T = self.T
+        """Host half of predict(): `both` = cat(logits, boxes) [B, nq, T+4] on the CPU (per-image form: T = Tmax, whose
+        pad columns are -inf and never a row's maximum)."""
+        T = self.T if self.captions is None else self.Tmax
         res = []
         for b in range(both.shape[0]):
             prob = both[b, :, :T].sigmoid()

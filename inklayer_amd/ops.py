@@ -856,6 +856,27 @@ def biattn_wide(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, T: int, 
     return out_v, out_l
 
 
+def biattn_wide_varlen(qv16: torch.Tensor, kl16: torch.Tensor, B: int, S: int, Tmax: int, t_len: torch.Tensor,
+                       scale: float):
+    """biattn_wide for a batch whose captions differ in length: kl16 f16 [B*Tmax, 2048] holds image b's t_len[b] text
+    rows at b*Tmax (the pad rows behind them are never read), t_len int32 [B] on the device (clamped into 1..Tmax by
+    the kernels).  -> (out_v f16 [B*S, 1024]; out_l f16 [B*Tmax, 1024] with zeros in the pad rows).  Image b's results
+    are bitwise those of biattn_wide(B=1, T=t_len[b]) on its rows."""
+    assert qv16.dtype == F16 and qv16.is_contiguous() and kl16.dtype == F16 and kl16.is_contiguous()
+    assert tuple(qv16.shape) == (B * S, 2048) and tuple(kl16.shape) == (B * Tmax, 2048)
+    dev = qv16.device
+    assert t_len.dtype == torch.int32 and t_len.is_contiguous() and tuple(t_len.shape) == (B,) and t_len.device == dev
+    need = C.c_int64(0)
+    check(_lib.lib().ink_biattn_wide_workspace(B, S, Tmax, C.byref(need)), "ink_biattn_wide_workspace")
+    ws = torch.empty(need.value, device=dev, dtype=F32)
+    out_v = torch.empty((B * S, 1024), device=dev, dtype=F16)
+    out_l = torch.empty((B * Tmax, 1024), device=dev, dtype=F16)
+    check(_lib.lib().ink_biattn_wide_varlen(qv16.data_ptr(), kl16.data_ptr(), B, S, Tmax, t_len.data_ptr(), 1024, scale,
+                                            ws.data_ptr(), out_v.data_ptr(), out_l.data_ptr(), _stream()),
+          "ink_biattn_wide_varlen")
+    return out_v, out_l
+
+
 def fusion_fold(v: torch.Tensor, B: int, S: int, lnv_g: torch.Tensor, lnv_b: torch.Tensor, eps: float,
                 text_kv: torch.Tensor, T: int, Wqv: torch.Tensor, bqv: torch.Tensor, Wo: torch.Tensor, bo: torch.Tensor,
                 gamma_v: torch.Tensor, scale: float, pos: Optional[torch.Tensor] = None,
@@ -1026,6 +1047,31 @@ def attn_midkeys(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n
     check(_lib.lib().ink_attn_midkeys(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
                                       B, n_q, n_k, n_heads, head_dim, scale, _p(blocked), out.data_ptr(),
                                       out.stride(0), _stream()), "ink_attn_midkeys")
+    return out
+
+
+def attn_midkeys_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, n_heads: int, head_dim: int,
+                        scale: float, blocked: Optional[torch.Tensor] = None,
+                        k_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_midkeys with a mask per batch entry (blocked u8 [n_q, n_k] shared or [B, n_q, n_k]) and a key count per
+    batch entry (k_len int32 [B] on the device, clamped into 0..n_k by the kernel): the keys t >= k_len[b] do not exist
+    for entry b and their rows are never loaded.  Key rows stay at b*n_k + t.  A row with no allowed key gives zeros."""
+    for t in (q, k, v):
+        assert t.dtype == F16 and t.dim() == 2 and t.stride(1) == 1
+        assert t.data_ptr() % 16 == 0                      # 16-byte vector loads (the row strides: ld % 8 in the C entry)
+    n_q, n_k = q.shape[0] // B, k.shape[0] // B
+    out = torch.empty((B * n_q, n_heads * head_dim), device=q.device, dtype=F16)
+    bstride = 0
+    if blocked is not None:
+        assert blocked.dtype == torch.uint8 and blocked.is_contiguous() and blocked.device == q.device
+        assert tuple(blocked.shape) in ((n_q, n_k), (B, n_q, n_k))
+        bstride = n_q * n_k if blocked.dim() == 3 else 0
+    if k_len is not None:
+        assert k_len.dtype == torch.int32 and k_len.is_contiguous() and tuple(k_len.shape) == (B,) and k_len.device == q.device
+    check(_lib.lib().ink_attn_midkeys_varlen(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                                             v.stride(0), B, n_q, n_k, n_heads, head_dim, scale, _p(blocked), bstride,
+                                             _p(k_len), out.data_ptr(), out.stride(0), _stream()),
+          "ink_attn_midkeys_varlen")
     return out
 
 

@@ -4,7 +4,12 @@ Reports, for 800 x 800 images and random weights (the time does not depend on th
   * detector forward, ms, at B = 1 and B = 8 for captions of T = 4 (both fusion paths: folded, and unfolded on
     ops.biattn_wide), 17, 64 and 256 tokens - eager, allow_graph=False, so that every T is measured the same way;
   * ops.biattn_wide alone at S = 13294 for the same T, next to its byte floor: QV read twice for q (both passes) and
-    once for values_v, out_v written once - 8 KiB per image token - over 8 TB/s.
+    once for values_v, out_v written once - 8 KiB per image token - over 8 TB/s;
+  * the mixed batch (one caption per image, GDinoEngine.set_captions), captions of MIXED = 256, 64, 17, 17, 9, 9, 4, 4
+    tokens: (a) one B = 8 forward in the per-image form, (b) what a caller without it does - the eight B = 1 forwards,
+    one engine per caption so that no set_caption host time is counted, (c) B = 8 with all eight captions at 256
+    tokens, and (d) ops.biattn_wide_varlen alone at B = 8, S = 13294 for the mixed lengths against the uniform T = 256
+    launch.  `--mixed-only` runs only this part.
 Every case is warmed up; the cases are then timed in alternation over several rounds with device events, and the
 median and the spread (min .. max) of the rounds are printed."""
 import statistics
@@ -16,6 +21,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 HBM_BYTES_PER_S = 8e12
 TS = (4, 17, 64, 256)
+MIXED = (256, 64, 17, 17, 9, 9, 4, 4)
 
 
 def caption_ids(T: int):
@@ -54,7 +60,39 @@ def show(title, res, floors=None):
         print(f"  {name:44s} {med:8.3f} ms  ({min(ms):.3f} .. {max(ms):.3f}){extra}")
 
 
-def main(rounds: int = 7) -> None:
+def mixed_batch(rounds: int, dev, cfg, sd, hw) -> None:
+    """The mixed-batch cases (a) - (d) of the module docstring."""
+    from inklayer_amd import gdino, ops, synthetic, weights_init
+    B, S, sc = len(MIXED), 13294, 256 ** -0.5
+    g = torch.Generator(device=dev).manual_seed(1)
+    qv = torch.randn((B * S, 2048), generator=g, device=dev).half()
+    kl = torch.randn((B * 256, 2048), generator=g, device=dev).half()
+    t_len = torch.tensor(MIXED, dtype=torch.int32, device=dev)
+    cases = {f"(d) biattn_wide_varlen B={B} S={S} mixed": lambda: ops.biattn_wide_varlen(qv, kl, B, S, 256, t_len, sc),
+             f"(d) biattn_wide B={B} S={S} T=256": lambda: ops.biattn_wide(qv, kl, B, S, 256, sc)}
+    show(f"bi-attention alone, B = {B}, lengths {MIXED}", timed(cases, rounds, 5))
+    del qv, kl, cases
+    torch.cuda.empty_cache()
+    imgs = [torch.from_numpy(synthetic.synthetic_sketch(i, hw[0], hw[1])).to(dev) for i in range(B)]
+    feats = {T: weights_init.random_text_features(cfg, dev, n_tokens=T) for T in set(MIXED)}
+    make = lambda T: gdino.GDinoEngine(sd, cfg, dev, encoded_text=feats[T], token_ids=caption_ids(T))   # noqa: E731
+    per_image, all_long = make(4), make(4)
+    per_image.set_captions([caption_ids(T) for T in MIXED], encoded_texts=[feats[T] for T in MIXED])
+    all_long.set_captions([caption_ids(256)] * B, encoded_texts=[feats[256]] * B)      # equal captions: the shared form
+    assert per_image.captions is not None and all_long.captions is None and all_long.T == 256
+    single = {T: make(T) for T in set(MIXED)}
+
+    def eight_single():
+        for im, T in zip(imgs, MIXED):
+            single[T].forward([im], allow_graph=False)
+
+    cases = {"(a) forward B=8, one caption per image": lambda: per_image.forward(imgs),
+             "(b) eight B=1 forwards, those captions": eight_single,
+             "(c) forward B=8, all captions T=256": lambda: all_long.forward(imgs, allow_graph=False)}
+    show(f"detector forward, {hw[0]} x {hw[1]}, eager, caption lengths {MIXED}", timed(cases, rounds, 1))
+
+
+def main(rounds: int = 7, mixed_only: bool = False) -> None:
     from inklayer_amd import gdino, ops, synthetic, weights_init
     if not torch.cuda.is_available():
         raise SystemExit("caption_time.py measures on the GPU: no device found")
@@ -62,6 +100,8 @@ def main(rounds: int = 7) -> None:
     cfg = gdino.GDinoConfig()
     sd = weights_init.random_gdino_state_dict(cfg, dev)
     hw = (800, 800)
+    if mixed_only:
+        return mixed_batch(rounds, dev, cfg, sd, hw)
     # ---- the kernel alone
     S, sc = 13294, 256 ** -0.5
     g = torch.Generator(device=dev).manual_seed(0)
@@ -87,7 +127,8 @@ def main(rounds: int = 7) -> None:
         show(f"detector forward, {hw[0]} x {hw[1]}, eager", timed(cases, rounds, 3 if B == 1 else 1))
         del engines, cases
         torch.cuda.empty_cache()
+    mixed_batch(rounds, dev, cfg, sd, hw)
 
 
 if __name__ == "__main__":
-    main()
+    main(mixed_only="--mixed-only" in sys.argv[1:])
