@@ -423,6 +423,45 @@ int ink_attn_midkeys_varlen(const void* Q, int64_t ldq, const void* K, int64_t l
                             const uint8_t* blocked, int64_t blocked_batch_stride, const int32_t* k_len,
                             void* O, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The caption encoder (csrc/text_bert.hip): BERT as GD/.../bertwarper.py:31-166 runs it, for a batch of captions PACKED
+ * row after row (caption b owns rows row_start[b] .. row_start[b+1]).  The rest of a layer is ink_gemm_f16 on split-f16
+ * operands, ink_layernorm_rows and ink_add_split_f16 (inklayer_amd/text_encoder.py).  (Two more entry points of ABI
+ * 10: nothing existing changes.)
+ *
+ * ink_text_embed_ln - HF BertEmbeddings.forward (word_embeddings(input_ids) + token_type_embeddings(0) +
+ * position_embeddings(position_ids), LayerNorm; the position ids are bertwarper.py:224-273's, restarting per phrase):
+ *   out[r] = LN(word[ids[r]] + pos[pos_ids[r]] + type_row) * gamma + beta     for R token rows.
+ * ids / pos_ids: int32 [R] ON THE DEVICE; the kernel clamps them into 0..V-1 / 0..P-1, so that bad device data cannot
+ * index out of range.  word f32 [V, C], pos f32 [P, C], type_row / gamma / beta f32 [C]; C % 4 == 0, C <= 2048; eps is
+ * BERT's 1e-12.  One pass writes out_f32 [R, C] (the residual of the first layer) and out_split_f16 [R, 3C], the
+ * split-f16 operand in ink_add_split_f16's layout.  Returns 1 with nothing launched for a null pointer, R / V / P < 1,
+ * a bad C, or a base that is not 16-byte aligned (ids / pos_ids: 4). */
+int ink_text_embed_ln(const int32_t* ids, const int32_t* pos_ids, int32_t R, const float* word, int32_t V,
+                      const float* pos, int32_t P, const float* type_row, const float* gamma, const float* beta,
+                      float eps, int32_t C, float* out_f32, void* out_split_f16, void* stream);
+
+/* ink_attn_text_f32 - HF BertSelfAttention.forward with the sub-sentence block mask of bertwarper.py:117-126 (the
+ * additive -inf mask built from generate_masks_with_special_tokens_and_transfer_map): softmax(scale q k^T, blocked ->
+ * -inf) v per caption and head, f32 math throughout.  Q / K / V: f32 rows read IN PLACE from the packed qkv projection
+ * (ld = 3 * n_heads * 64), head h at columns [64 h, 64 h + 64); head_dim must be 64, n_heads >= 1.  row_start: int32
+ * [B + 1] ON THE DEVICE; at most Tmax <= 256 rows per caption, R rows in all: the kernel clamps every start into 0..R
+ * and every count into 0..min(Tmax, R - start).  blocked: u8 [Tmax, Tmax] per caption, blocked_batch_stride BYTES apart
+ * (0: one shared matrix; NULL: none, and the stride must be 0), the conventions of ink_attn_midkeys_varlen; a row with
+ * no allowed key gives zeros, and a blocked key's rows reach no output.  out_split_f16 [R, >= 3 * n_heads * 64] (row
+ * stride ldo halves) receives the context as the split-f16 operand of the output projection: head h fills its 64
+ * columns in each of the three segments; out_f32 (row stride ldf; NULL to skip) an f32 copy.  A workgroup takes one
+ * (caption, head, 64 queries), stages that head's K and V through LDS in tiles of 64 keys and skips a tile none of its
+ * queries may see; all its bounds come from its own caption, so caption b's results are bitwise those of a B = 1
+ * launch on that caption alone.  Returns 1 with nothing launched for a null pointer, head_dim != 64, B outside
+ * 1..65535, Tmax outside 1..256, R < 1, ldq / ldk / ldv / ldf not a multiple of 4 or ldo not a multiple of 8, a
+ * negative stride, or a base that is not 16-byte aligned (row_start: 4). */
+int ink_attn_text_f32(const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv,
+                      const int32_t* row_start /* device, [B + 1] */, int32_t B, int32_t R, int32_t Tmax,
+                      int32_t n_heads, int32_t head_dim, float scale, const uint8_t* blocked,
+                      int64_t blocked_batch_stride, void* out_split_f16, int64_t ldo, float* out_f32, int64_t ldf,
+                      void* stream);
+
 /* softmax(scale q k^T) v for n_q <= 16 queries per batch entry against MANY keys (SAM decoder tokens ->
  * image: 7..16 x 4096, SA/modeling/transformer.py:163-168) on f32 rows: head h at columns [h*hd,(h+1)*hd), head_dim
  * must be 16 and n_heads a multiple of 4; q_batch_rows / kv_batch_rows as in InkAttn; O dense [n_batch*n_q, ..].

@@ -116,6 +116,10 @@ SIGNATURES = {
                                c_void_p, c_void_p],
     "ink_attn_midkeys_varlen": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
                                 c_float, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p],
+    "ink_text_embed_ln": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                          c_float, c_int, c_void_p, c_void_p, c_void_p],
+    "ink_attn_text_f32": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                          c_float, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p],
     "ink_attn_fewq": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
                       c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "ink_topk_rowmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

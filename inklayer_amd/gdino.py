@@ -574,42 +574,80 @@ class GDinoEngine:
     caption_cache_size = 8
     tokenizer = None         # anything with decode(ids) -> str (inklayer_amd.wordpiece.WordPiece): predict's phrases as text
 
+    text_encoder = "auto"    # where BERT + feat_map of a caption run: "gpu" (inklayer_amd/text_encoder.py: every missing
+    #                          caption of a call in ONE pass on the library's kernels), "host" (text_branch.py: f32 torch
+    #                          on the CPU, one caption at a time) or "auto": the GPU encoder where the engine is on a GPU,
+    #                          text_weights holds a 768-wide BERT and the library is built, the host fold otherwise
+    _text_enc = None         # the BertTextEncoder of text_weights: built on the first miss, dropped with them
+
     def set_caption(self, token_ids: Sequence[int], sd: Optional[Dict[str, torch.Tensor]] = None,
                     encoded_text: Optional[torch.Tensor] = None) -> None:
         """Switch the engine to the caption with these token ids ([CLS] ... [SEP], at most cfg.max_text_len are kept).
-        Its text features are encoded_text [T, 256] where given, else feat_map(BERT(ids)) folded on the host from the
-        checkpoint's bert.* / feat_map.* tensors (text_branch.encode_caption_from_checkpoint; sd is remembered from
-        the first call that passes one) - once per caption: the last `caption_cache_size` captions are kept.  BERT
-        is host-side torch and not on the hot path.  The shared-caption form, see set_text; set_captions takes one
-        caption per image."""
+        Its text features are encoded_text [T, 256] where given, else feat_map(BERT(ids)) from the checkpoint's bert.* /
+        feat_map.* tensors (sd is remembered from the first call that passes one), on the GPU encoder or folded on the
+        host as `text_encoder` says - once per caption: the last `caption_cache_size` captions are kept, as host
+        copies.  The shared-caption form, see set_text; set_captions takes one caption per image."""
         ids = tuple(int(t) for t in token_ids)[:self.cfg.max_text_len]
         self._take_text_weights(sd)
-        self.set_text(self._caption_features(ids, encoded_text), ids)
+        self.set_text(self._captions_features([ids], [encoded_text])[0], ids)
 
     def _take_text_weights(self, sd: Optional[Dict[str, torch.Tensor]]) -> None:
         if sd is not None:
             sd = clean_state_dict(sd)
             self.text_weights = {k: v for k, v in sd.items() if k.startswith(("bert.", "feat_map."))}
             self._captions.clear()                          # features folded from another checkpoint
+            self.release_text_encoder()                     # ... and an encoder built from it
 
-    def _caption_features(self, ids: Tuple[int, ...], encoded_text: Optional[torch.Tensor]) -> torch.Tensor:
-        """[len(ids), 256] text features of an (already truncated) caption: the given ones, the cache's, or BERT's."""
-        if encoded_text is None:
-            encoded_text = self._captions.get(ids)
-        if encoded_text is None:
+    def release_text_encoder(self) -> None:
+        """Drop the GPU text encoder (about 0.6 GB for BERT-base); the next caption that misses the cache builds it
+        again from text_weights."""
+        self._text_enc = None
+
+    def _gpu_text(self) -> bool:
+        """Does a cache miss go to the GPU encoder?  (text_encoder, see there.)"""
+        mode = self.text_encoder
+        if mode not in ("auto", "gpu", "host"):
+            raise ValueError(f'text_encoder is "auto", "gpu" or "host", not {mode!r}')
+        if mode == "gpu" and self.dev.type != "cuda":
+            raise ValueError('text_encoder = "gpu" needs an engine on a GPU; this one is on ' + str(self.dev))
+        if mode == "host" or self.dev.type != "cuda":
+            return False
+        from . import _lib
+        from .text_encoder import HIDDEN, bert_hidden_size
+        able = bool(self.text_weights) and bert_hidden_size(self.text_weights) == HIDDEN and _lib.lib_path().exists()
+        if mode == "gpu" and not able:
+            raise ValueError('text_encoder = "gpu" needs the built library and a state dict with a 768-wide bert.*')
+        return able
+
+    def _captions_features(self, caps: Sequence[Tuple[int, ...]],
+                           encoded_texts: Sequence[Optional[torch.Tensor]]) -> List[torch.Tensor]:
+        """[len(ids), 256] text features of every (already truncated) caption: the given ones, the cache's, or BERT's.
+        The captions found in neither are encoded together, each distinct one once."""
+        gpu = self._gpu_text()
+        feats = [f if f is not None else self._captions.get(ids) for ids, f in zip(caps, encoded_texts)]
+        missing = list(dict.fromkeys(ids for ids, f in zip(caps, feats) if f is None))
+        if missing:
             if not self.text_weights:
                 raise ValueError("set_caption needs encoded_text [T, 256] or a state dict with the checkpoint's bert.* "
                                  "and feat_map.* tensors")
-            from .text_branch import encode_caption_from_checkpoint
-            encoded_text = encode_caption_from_checkpoint(self.text_weights, ids)
-        return encoded_text[:len(ids)]
+            if gpu:
+                if self._text_enc is None:
+                    from .text_encoder import BertTextEncoder
+                    self._text_enc = BertTextEncoder(self.text_weights, self.dev)
+                new = [f.to("cpu", F32) for f in self._text_enc.encode(missing)]
+            else:
+                from .text_branch import encode_caption_from_checkpoint
+                new = [encode_caption_from_checkpoint(self.text_weights, ids) for ids in missing]
+            new = dict(zip(missing, new))
+            feats = [f if f is not None else new[ids] for ids, f in zip(caps, feats)]
+        return [f[:len(ids)] for ids, f in zip(caps, feats)]
 
     def set_captions(self, token_id_lists: Sequence[Sequence[int]], sd: Optional[Dict[str, torch.Tensor]] = None,
                      encoded_texts: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """One caption PER IMAGE of the next batch (GroundingDINO.forward with a list of captions,
         groundingdino.py:243-279): token_id_lists[i] belongs to image i of the next forward / predict, each truncated
-        to cfg.max_text_len; features from encoded_texts[i], the caption cache or BERT folded on the host, as
-        set_caption finds them.  Equal captions are the shared form: set_caption and its paths, bit for bit.
+        to cfg.max_text_len; features from encoded_texts[i], the caption cache or BERT, as set_caption finds them (the
+        captions that miss both are encoded in one pass, equal ones once).  Equal captions are the shared form: set_caption and its paths, bit for bit.
         Otherwise the engine enters the per-image form, the reference's padding="longest" batch with Tmax = max T_b:
           text0 [B*Tmax, 256] (pad rows zero), t_len int32 [B] on the device, text_blocked u8 [B, Tmax, Tmax] (each
           caption's block-diagonal mask in the corner; pad rows and columns blocked except the diagonal, which is what
@@ -628,7 +666,7 @@ class GDinoEngine:
         if len(set(caps)) == 1:
             return self.set_caption(caps[0], sd=sd, encoded_text=feats_in[0])
         self._take_text_weights(sd)
-        feats = [self._caption_features(ids, f).detach().to("cpu", F32) for ids, f in zip(caps, feats_in)]
+        feats = [f.detach().to("cpu", F32) for f in self._captions_features(caps, feats_in)]
         for ids, f in zip(caps, feats):
             assert f.shape[0] == len(ids), "one feature row per token id"
             self._captions.put(ids, f)

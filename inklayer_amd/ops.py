@@ -1075,6 +1075,67 @@ def attn_midkeys_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B:
     return out
 
 
+def text_embed_ln(ids, pos_ids, word: torch.Tensor, pos: torch.Tensor, type_row: torch.Tensor, gamma: torch.Tensor,
+                  beta: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """BERT's embedding block for R packed token rows: LN(word[ids] + pos[pos_ids] + type_row) * gamma + beta ->
+    (f32 [R, C], split-f16 operand [R, 3C] as add_split_f16 lays it out).  ids / pos_ids: sequences of ints or host
+    tensors (checked against the tables here: ValueError before any launch, then uploaded) or int32 device tensors
+    (the kernel clamps those into range)."""
+    V, Cn = word.shape
+    P = pos.shape[0]
+    dev = word.device
+    for t, n in ((word, V), (pos, P)):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (n, Cn)
+    for t in (type_row, gamma, beta):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == Cn and t.device == dev
+    dev_ids = []
+    for t, n, what in ((ids, V, "token id"), (pos_ids, P, "position id")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            t = torch.as_tensor(t, dtype=torch.int64).reshape(-1)
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+                raise ValueError(f"{what} outside 0..{n - 1}")
+            t = t.to(torch.int32).to(dev)
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == dev
+        dev_ids.append(t)
+    R = dev_ids[0].numel()
+    assert R >= 1 and dev_ids[1].numel() == R
+    out = torch.empty((R, Cn), device=dev, dtype=F32)
+    split = torch.empty((R, 3 * Cn), device=dev, dtype=F16)
+    check(_lib.lib().ink_text_embed_ln(dev_ids[0].data_ptr(), dev_ids[1].data_ptr(), R, word.data_ptr(), V,
+                                       pos.data_ptr(), P, type_row.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps,
+                                       Cn, out.data_ptr(), split.data_ptr(), _stream()), "ink_text_embed_ln")
+    return out, split
+
+
+def attn_text_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, row_start: torch.Tensor, *, Tmax: int,
+                  n_heads: int, scale: float, blocked: Optional[torch.Tensor] = None,
+                  want_f32: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """BERT's self-attention for packed captions on f32 rows [R, n_heads * 64] (views into the fused qkv projection;
+    head_dim 64): caption b owns rows row_start[b] .. row_start[b + 1] (int32 [B + 1] on the device, at most Tmax <= 256
+    rows each).  blocked: u8 [Tmax, Tmax] shared or [B, Tmax, Tmax].  -> (split-f16 operand [R, 3 * n_heads * 64] of the
+    context, its f32 copy [R, n_heads * 64] or None).  A row with no allowed key gives zeros."""
+    E = n_heads * 64
+    for t in (q, k, v):
+        assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == E
+        assert t.data_ptr() % 16 == 0                      # 16-byte vector loads (the row strides: ld % 4 in the C entry)
+    R = q.shape[0]
+    assert k.shape[0] == R and v.shape[0] == R
+    assert row_start.dtype == torch.int32 and row_start.dim() == 1 and row_start.is_contiguous() and row_start.device == q.device
+    B = row_start.numel() - 1
+    bstride = 0
+    if blocked is not None:
+        assert blocked.dtype == torch.uint8 and blocked.is_contiguous() and blocked.device == q.device
+        assert tuple(blocked.shape) in ((Tmax, Tmax), (B, Tmax, Tmax))
+        bstride = Tmax * Tmax if blocked.dim() == 3 else 0
+    out = torch.empty((R, 3 * E), device=q.device, dtype=F16)
+    out32 = torch.empty((R, E), device=q.device, dtype=F32) if want_f32 else None
+    check(_lib.lib().ink_attn_text_f32(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                       row_start.data_ptr(), B, R, Tmax, n_heads, 64, scale, _p(blocked), bstride,
+                                       out.data_ptr(), out.stride(0), _p(out32), E if want_f32 else 0, _stream()),
+          "ink_attn_text_f32")
+    return out, out32
+
+
 def attn_fewq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, n_batch: int, n_heads: int, head_dim: int,
               scale: float, n_q: int, n_k: int, q_batch_rows: Optional[torch.Tensor] = None,
               kv_batch_rows: Optional[torch.Tensor] = None, k_add: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -4,7 +4,9 @@ InkLayer always prompts with the caption "object" (InkLayer/detector/gdino.py:18
 `encoded_text = feat_map(BERT(tokens))` does not depend on the image: it is computed ONCE when a
 checkpoint is loaded (plain torch on the host: ~0.7 GFLOP, never on the hot path) and handed to the
 detector engine as a [n_tokens, 256] tensor.  Any other caption (GDinoEngine.set_caption, up to 256 token ids) is folded
-the same way, once per caption; text becomes ids in inklayer_amd/wordpiece.py.
+the same way, once per caption, by an engine without a GPU or with text_encoder = "host"; on a GPU engine fresh captions
+run through inklayer_amd/text_encoder.py (the same forward on the library's kernels, a batch in one pass).  Text becomes
+ids in inklayer_amd/wordpiece.py.
 
 Parity: this restatement of BertModelWarper.forward (GD/.../bertwarper.py:31-166: HF BertModel with the
 sub-sentence block attention mask and explicit position ids) is pinned against `transformers.BertModel` itself on

@@ -232,3 +232,39 @@ def random_depth_state_dict(cfg, device, seed: int = 3) -> Dict[str, torch.Tenso
         if k.endswith("gamma"):
             sd[k] = 0.5 + 0.2 * sd[k]          # LayerScale
     return sd
+
+
+def random_bert_state_dict(n_layers: int = 12, vocab_size: int = 30522, seed: int = 0,
+                           feat_map: bool = True) -> Dict[str, torch.Tensor]:
+    """A seeded random BERT of GroundingDINO's text branch under the checkpoint's key names (`bert.*` as HF BertModel
+    names them, plus `feat_map.*` [256, 768]) on the host, without importing transformers: 768 hidden, 12 heads, 3072
+    intermediate, 512 positions.  HF's initialisation (normal(0, 0.02) matrices, unit LayerNorm), then the LayerNorm
+    weights perturbed by 0.1 randn and every bias by 0.05 randn so that no term of the forward is trivial."""
+    g = torch.Generator().manual_seed(seed)
+    D, I = 768, 3072
+    rn = lambda *shape: torch.randn(shape, generator=g, dtype=torch.float32)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def lin(name, n_out, n_in):
+        sd[name + ".weight"], sd[name + ".bias"] = 0.02 * rn(n_out, n_in), 0.05 * rn(n_out)
+
+    def norm(name):
+        sd[name + ".weight"], sd[name + ".bias"] = 1.0 + 0.1 * rn(D), 0.05 * rn(D)
+
+    e = "bert.embeddings."
+    sd[e + "word_embeddings.weight"] = 0.02 * rn(vocab_size, D)
+    sd[e + "position_embeddings.weight"] = 0.02 * rn(512, D)
+    sd[e + "token_type_embeddings.weight"] = 0.02 * rn(2, D)
+    norm(e + "LayerNorm")
+    for i in range(n_layers):
+        p = f"bert.encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            lin(p + "attention.self." + n, D, D)
+        lin(p + "attention.output.dense", D, D)
+        norm(p + "attention.output.LayerNorm")
+        lin(p + "intermediate.dense", I, D)
+        lin(p + "output.dense", D, I)
+        norm(p + "output.LayerNorm")
+    if feat_map:
+        sd["feat_map.weight"], sd["feat_map.bias"] = rn(256, D) / math.sqrt(D), 0.05 * rn(256)
+    return sd
