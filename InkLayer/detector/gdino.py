@@ -8,7 +8,13 @@ HBM (the reference re-`.to(device)`s it every call, GD/util/inference.py:64).
 `predict(model, image, caption, box_threshold, text_threshold)` is the reference's open-vocabulary call
 (GD/util/inference.py:54-97): any caption of up to 256 tokens, a phrase per box.  `run_gdino_on_sketch` wraps it in
 run_ft_dino_on_sketch's dict shape with the real labels.  `predict_batch` / `run_gdino_on_sketches` take a batch of
-images with one caption each and run it as one forward (per-image token counts and text padding masks)."""
+images with one caption each and run it as one forward (per-image token counts and text padding masks).
+
+Closed-set detection - a class index per box, scored as the reference's evaluation does (PostProcessCocoGrounding,
+GD/demo/test_ap_on_coco.py:66-137) with the scores, the selection and the box conversion on the GPU:
+`predict_classes(model, image, classes, num_select=300)`, `predict_classes_batch` (one class list per image),
+`predict_spans` (the given-phrase mode of GD/demo/inference_on_a_image.py:117-142) and `run_gdino_on_sketch_classes(path,
+nouns, score_threshold=0.2)`, the dict of the reference's closed-set detector (InkLayer/detector/gdino_mmdetection.py)."""
 import os
 import re
 
@@ -194,6 +200,118 @@ def predict_batch(model, images, captions, box_threshold, text_threshold, remove
             rows = held_text.view(len(held_caps), held_tmax, 256)
             model.set_captions(held_caps, encoded_texts=[rows[b, :n] for b, n in enumerate(held_lens)])
         model.tokenizer = held_tok
+
+
+class _held_text:
+    """with _held_text(model): ... - the engine leaves with the caption(s), features and tokenizer it came with, in the
+    shared and in the per-image form (the features travel along: many captions may push them out of the cache)."""
+
+    def __init__(self, model):
+        self.m = model
+
+    def __enter__(self):
+        m = self.m
+        self.held = (m.tokenizer, m.captions, m.token_ids, m.text0.cpu(), m.t_lens, m.Tmax)
+        return m
+
+    def __exit__(self, *exc):
+        m = self.m
+        tok, caps, ids, text, lens, tmax = self.held
+        if caps is None:
+            if m.captions is not None or tuple(m.token_ids) != tuple(ids):
+                m.set_caption(ids, encoded_text=text)
+        else:
+            rows = text.view(len(caps), tmax, 256)
+            m.set_captions(caps, encoded_texts=[rows[b, :n] for b, n in enumerate(lens)])
+        m.tokenizer = tok
+        return False
+
+
+def _class_prompt(model, classes):
+    """A closed_set.ClassPrompt as it is, or the prompt of a list of class names (needs the vocabulary, as a caption
+    given as text does)."""
+    from inklayer_amd import closed_set
+    if isinstance(classes, closed_set.ClassPrompt):
+        return classes
+    if isinstance(classes, str):
+        raise TypeError("classes is a list of class names, not one string")
+    return closed_set.class_prompt(get_tokenizer(), list(classes), model.cfg.max_text_len)
+
+
+def _load_resized(model, image):
+    """(resized HWC uint8 image on the engine's device, (h, w) of the original) of an array or a path."""
+    import torch
+    from inklayer_amd import gdino, ops
+    if isinstance(image, (str, os.PathLike)):
+        image = np.asarray(Image.open(image).convert("RGB"))
+    raw = torch.from_numpy(np.ascontiguousarray(image)).to(model.dev)
+    oh, ow = gdino.resize_shape(image.shape[1], image.shape[0])
+    return ops.resize_bilinear_u8(raw, oh, ow), (int(image.shape[0]), int(image.shape[1]))
+
+
+def _set_prompts(model, prompts):
+    """The engine's caption(s) := the prompts' (stand-in features under INKLAYER_RANDOM_WEIGHTS=1, as predict)."""
+    texts = [None] * len(prompts)
+    if os.environ.get("INKLAYER_RANDOM_WEIGHTS") == "1":
+        from inklayer_amd import weights_init
+        texts = [weights_init.random_text_features(model.cfg, "cpu", n_tokens=len(p.token_ids)) for p in prompts]
+    if len(prompts) == 1:
+        if model.captions is not None or tuple(model.token_ids) != tuple(prompts[0].token_ids):
+            model.set_caption(prompts[0].token_ids, encoded_text=texts[0])
+    else:
+        model.set_captions([p.token_ids for p in prompts], encoded_texts=texts)
+
+
+def predict_classes_batch(model, images, class_lists, num_select=300, normalized=False):
+    """Closed-set detection for a batch with ONE CLASS LIST PER IMAGE, as one forward: images are HWC uint8 RGB arrays
+    or paths, class_lists[i] the class names of image i (or a closed_set.ClassPrompt).  -> [(boxes xyxy [k, 4] in the
+    pixels of the original image - normalised with normalized=True -, scores [k] descending, labels int64 [k] indexing
+    class_lists[i])], k = min(num_select, num_queries * len(classes)): PostProcessCocoGrounding's result
+    (GD/demo/test_ap_on_coco.py:66-137) with the image's own classes.  Stateless like predict."""
+    images, class_lists = list(images), list(class_lists)
+    if len(images) != len(class_lists):
+        raise ValueError(f"{len(images)} images for {len(class_lists)} class lists: one class list per image")
+    if not images:
+        return []
+    prompts = [_class_prompt(model, c) for c in class_lists]
+    loaded = [_load_resized(model, im) for im in images]
+    with _held_text(model):
+        _set_prompts(model, prompts)
+        maps = [p.positive_map for p in prompts]
+        return model.predict_classes([r for r, _ in loaded], maps, num_select,
+                                     None if normalized else [s for _, s in loaded])
+
+
+def predict_classes(model, image, classes, num_select=300, normalized=False):
+    """Closed-set detection of one image: which of `classes` is each box.  See predict_classes_batch."""
+    return predict_classes_batch(model, [image], [classes], num_select, normalized)[0]
+
+
+def predict_spans(model, image, caption, token_spans, box_threshold):
+    """The given-phrase mode of the reference's demo (GD/demo/inference_on_a_image.py:117-142): token_spans is one list
+    of (start, end) character spans per phrase, positions in the caption as predict preprocesses it (lower-cased,
+    stripped, a trailing ".").  -> (boxes [n, 4] cxcywh normalised, scores [n], phrases [n]): for every phrase, in
+    order, the queries whose phrase score exceeds box_threshold, each with the phrase's text.  Needs the vocabulary.
+    Stateless like predict."""
+    from inklayer_amd import closed_set
+    prompt = closed_set.span_prompt(get_tokenizer(), caption, token_spans, model.cfg.max_text_len)
+    resized, _ = _load_resized(model, image)
+    with _held_text(model):
+        _set_prompts(model, [prompt])
+        boxes, scores, which = model.predict_spans([resized], prompt.positive_map, box_threshold)[0]
+    return boxes, scores, [prompt.names[i] for i in which.tolist()]
+
+
+def run_gdino_on_sketch_classes(sketch_path, nouns, score_threshold=0.2, num_select=300):
+    """The reference's closed-set detector call (InkLayer/detector/gdino_mmdetection.py:25-98:
+    run_ft_dino_inference_on_image(image_path, nouns, ...)) on this engine: {"bboxes": normalised xyxy lists, "labels":
+    nouns[label] per box, "scores"}: the best num_select (query, class) pairs with a score >= score_threshold, best
+    first."""
+    boxes, scores, labels = predict_classes(get_model(), sketch_path, nouns, num_select, normalized=True)
+    names = nouns.names if hasattr(nouns, "names") else list(nouns)
+    keep = scores >= score_threshold
+    return {"bboxes": boxes[keep].tolist(), "labels": [names[i] for i in labels[keep].tolist()],
+            "scores": scores[keep].tolist()}
 
 
 def run_gdino_on_sketches(paths, captions, box_threshold=0.2, text_threshold=0.0):

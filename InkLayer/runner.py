@@ -48,7 +48,7 @@ def _tick(name, t0):
 
 
 def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_intermediate=False, inpaint=False,
-                  masks_dev=None, flush_files=True):
+                  masks_dev=None, flush_files=True, json_labels=False):
     """Everything of run_inklayer_pipeline after the detector and the segmentor have answered (runner.py:35-101): the
     output tree of the detection stage, then the refinement stage.  Shared by the per-file entry point below and by the
     batched directory runner (inklayer_amd/batch_runner.py), so both write the same tree.  masks_dev (optional): the same
@@ -62,7 +62,8 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
         t0 = time.perf_counter()
         boxes_int = [[int(v) for v in box] for box in boxes_tensor.tolist()]
         save_norm_bboxes(bboxes_list=boxes_int, scores_list=dino_out["scores"], input_pil=input_pil,
-                         out_path=os.path.join(out_dir, "bboxes.json"))
+                         out_path=os.path.join(out_dir, "bboxes.json"),
+                         labels=list(dino_out["labels"]) if json_labels else None)    # closed-set run: the class names
         import numpy as np
         masks_dir = os.path.join(out_dir, "masks")
         os.makedirs(masks_dir, exist_ok=True)
@@ -141,15 +142,23 @@ def finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_inter
     return out_dir
 
 
-def run_inklayer_pipeline(input_path, out_base_dir, no_intermediate=False, inpaint=False):
+def run_inklayer_pipeline(input_path, out_base_dir, no_intermediate=False, inpaint=False, classes=None):
+    """classes (a list of class names): the detector leg is the closed-set one, run_gdino_on_sketch_classes - each box
+    is one of these classes, bboxes.json gets a "labels" list and bboxes.png the names.  None: the "object" detector,
+    as the reference's runner."""
     out_dir, input_pil = _prepare_out_dir(input_path, out_base_dir, wait=False)      # (finish_sketch flushes)
     # detector -> boxes (runner.py:34-44): JSON gets the int()-truncated pixel boxes, SAM the float ones
-    dino_out = run_ft_dino_on_sketch(sketch_path=input_path)
+    if classes is not None:
+        from InkLayer.detector.gdino import run_gdino_on_sketch_classes
+        dino_out = run_gdino_on_sketch_classes(input_path, list(classes))
+    else:
+        dino_out = run_ft_dino_on_sketch(sketch_path=input_path)
     boxes_tensor, phrases = process_dino_output(dino_out, input_pil)
     # segmentor -> masks (runner.py:49-64)
     input_pil = Image.open(input_path).convert("RGB")
     masks_np = run_SAM(image_pil=input_pil, boxes_filt=boxes_tensor)
-    return finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_intermediate, inpaint)
+    return finish_sketch(out_dir, input_pil, dino_out, boxes_tensor, masks_np, no_intermediate, inpaint,
+                         json_labels=classes is not None)
 
 
 def run_inpaint_single_layer(request_data, cur_dir, out_dir):

@@ -555,6 +555,29 @@ int ink_sine_embed4(const float* ref, const float* dim_t, int32_t N, void* out_f
 int ink_box_refine(const float* delta, int64_t ldd, const float* ref, int32_t N, int32_t ref_is_logit,
                    float* out, void* stream);
 
+/* Closed-set class scoring (PostProcessCocoGrounding.forward, GD/demo/test_ap_on_coco.py:99-106; the given-phrase mode
+ * of GD/demo/inference_on_a_image.py:117-124):
+ *     out[b, q, c] = sum_t sigmoid(logits[b, q, t]) * pos_map[c, t]          f32 [B, nq, C]
+ * logits f32 [B, nq, T], row (b, q) at logits + (b * nq + q) * ld_row, ld_row >= T, T <= 256 and in no way aligned;
+ * pos_map f32 [C, T] shared by the images (pm_image_stride == 0) or [B, C, T] with image b's map at
+ * pos_map + b * pm_image_stride (>= C * T; rows of classes an image does not have are zero or cut off by n_cls);
+ * n_cls int32 [B] or NULL: classes c >= n_cls[b] of image b score -1.0, below every real score (those are >= 0).
+ * A -inf logit contributes exactly 0 and a +inf logit exactly pos_map[c, t]; no NaN-free input makes a NaN.  The sum
+ * runs in f32 in an order that depends on t alone (four terms per lane upwards, then a 64-lane butterfly), so zero
+ * terms - pad columns, entries outside a class's span - change no bit, and an image's scores do not depend on B, on
+ * the other images or on how far T is padded.  All pointers 4-byte aligned; B <= 65535; nq * C < 2^31. */
+int ink_class_scores(const float* logits, int64_t ld_row, const float* pos_map, int64_t pm_image_stride,
+                     const int32_t* n_cls, int32_t B, int32_t nq, int32_t T, int32_t C, float* out, void* stream);
+
+/* The boxes of the selected (query, class) pairs (test_ap_on_coco.py:118-132): idx int32 [B, K] = query * Cmax + class
+ * (ink_topk_rowmax over the scores viewed as [B, nq * Cmax, 1]); boxes f32 [B, nq, 4] cxcywh; scale_wh f32 [B, 2] =
+ * (w, h) of each image ((1, 1): normalised).  out_boxes f32 [B, K, 4] = (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h)
+ * * (W, H, W, H) (box_ops.box_cxcywh_to_xyxy, then the scale), labels int32 [B, K] = idx % Cmax, query int32 [B, K] =
+ * idx / Cmax.  An index outside [0, nq * Cmax) reads nothing: zeros, label and query -1.  boxes / out_boxes 16-byte
+ * aligned; B * K <= 2^30. */
+int ink_select_boxes(const int32_t* idx, const float* boxes, const float* scale_wh, int32_t B, int32_t K, int32_t nq,
+                     int32_t Cmax, float* out_boxes, int32_t* labels, int32_t* query, void* stream);
+
 /* ------------------------------------------------------------------------
  * Mask hand-off stage of the refinement, on resident masks.  Integer / byte work, bit-exact with the
  * reference's cv2 results.

@@ -123,6 +123,9 @@ SIGNATURES = {
     "ink_attn_fewq": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int,
                       c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "ink_topk_rowmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ink_class_scores": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "ink_select_boxes": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                         c_void_p],
     "ink_sine_embed4": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "ink_box_refine": [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "ink_mask_cleanup_workspace_ints": [c_int, c_int, c_int, c_int, C.POINTER(c_i64)],

@@ -711,6 +711,93 @@ class GDinoEngine:
             res.append((both[b, keep, TL:], kept.max(dim=1)[0] if len(kept) else kept.new_zeros(0), phrases))
         return res
 
+    # ------------------------------------------------------------------ closed-set scoring (csrc/closed_set.hip)
+    def _positive_maps(self, positive_maps, B: int):
+        """positive_maps for a forward of B images -> (map f32 on the device, [C, T] shared or [B, Cmax, T] per image;
+        n_cls int32 [B] on the device or None; class counts).  ONE map [C, >= T] (a tensor) scores every image against
+        the same classes and needs the shared-caption form; a LIST of B maps [C_b, >= T_b] gives image b its own.  Maps
+        as wide as max_text_len (closed_set.positive_map_from_spans) are cut to the caption's T columns; a map that is
+        non-zero beyond its caption's tokens belongs to another caption: ValueError."""
+        T = self.T if self.captions is None else self.Tmax
+        t_of = [self.T] * B if self.captions is None else list(self.t_lens)
+
+        def cut(pm, Tb):
+            pm = torch.as_tensor(pm, dtype=F32).detach().cpu()
+            if pm.dim() != 2 or pm.shape[0] < 1 or pm.shape[1] < Tb:
+                raise ValueError(f"a positive map is [C >= 1, >= {Tb} token columns], not {tuple(pm.shape)}")
+            if bool((pm[:, Tb:] != 0).any()):
+                raise ValueError(f"a positive map marks tokens beyond its caption's {Tb}: it was built for another caption")
+            return pm[:, :Tb]
+
+        if not isinstance(positive_maps, (list, tuple)):
+            if self.captions is not None:
+                raise ValueError("one positive map for all images needs one caption for all images (set_caption); after "
+                                 "set_captions pass one map per image")
+            pm = cut(positive_maps, self.T)
+            return pm.contiguous().to(self.dev), None, [pm.shape[0]] * B
+        if len(positive_maps) != B:
+            raise ValueError(f"{len(positive_maps)} positive maps for {B} images")
+        maps = [cut(pm, t_of[b]) for b, pm in enumerate(positive_maps)]
+        counts = [m.shape[0] for m in maps]
+        full = torch.zeros((B, max(counts), T), dtype=F32)
+        for b, m in enumerate(maps):
+            full[b, :m.shape[0], :m.shape[1]] = m
+        return full.to(self.dev), torch.tensor(counts, dtype=I32).to(self.dev), counts
+
+    def predict_classes(self, images_u8: Sequence[torch.Tensor], positive_maps, num_select: int = 300,
+                        sizes: Optional[Sequence[Tuple[int, int]]] = None):
+        """PostProcessCocoGrounding.forward (GD/demo/test_ap_on_coco.py:99-137) on the GPU: the score of (query, class) is
+        sum_t sigmoid(logit[q, t]) * positive_map[c, t]; per image the num_select best pairs, best first (ties: the
+        lower query, then the lower class).  -> [(boxes xyxy f32 [k, 4], scores f32 [k], labels int64 [k])] with
+        k = min(num_select, nq * C_b); boxes in the pixels of sizes[b] = (h, w), normalised without sizes.
+        positive_maps: see _positive_maps.  Scores, selection and box conversion stay on the device; ONE copy of
+        [B, K, 6] (score, label, box) comes back."""
+        B, nq = len(images_u8), self.cfg.num_queries
+        pm, n_cls, counts = self._positive_maps(positive_maps, B)
+        if num_select < 1:
+            raise ValueError("num_select >= 1")
+        if sizes is not None and len(sizes) != B:
+            raise ValueError(f"{len(sizes)} sizes for {B} images")
+        Cmax = pm.shape[-2]
+        K = min(int(num_select), nq * Cmax)
+        nchunk = -(-(nq * Cmax) // 16384)               # ops.topk_rowmax's chunked form: every chunk holds K, the merge nchunk * K
+        if nchunk > 1 and (nchunk * K > 16384 or (nq * Cmax) // nchunk < K):
+            raise ValueError(f"num_select = {num_select} of {nq * Cmax} (query, class) pairs is more than the selection "
+                             f"kernel merges ({16384 // nchunk} here)")
+        scale = torch.ones((B, 2), dtype=F32) if sizes is None else \
+            torch.tensor([[float(w_), float(h)] for h, w_ in sizes], dtype=F32)
+        logits, boxes = self.forward(images_u8)
+        prob = ops.class_scores(logits, pm, n_cls)
+        idx, val = ops.topk_rowmax(prob.view(B, nq * Cmax, 1), K, want_values=True)
+        xyxy, labels, _ = ops.select_boxes(idx, boxes.contiguous(), scale.to(self.dev), Cmax)
+        out = torch.cat([val[..., None], labels.to(F32)[..., None], xyxy], dim=-1).cpu()       # single D2H copy
+        res = []
+        for b in range(B):
+            k = min(K, nq * counts[b])                  # classes c >= C_b score -1 and sort behind every real pair
+            res.append((out[b, :k, 2:].contiguous(), out[b, :k, 0].contiguous(), out[b, :k, 1].to(torch.int64)))
+        return res
+
+    def predict_spans(self, images_u8: Sequence[torch.Tensor], positive_maps, box_threshold: float):
+        """The given-phrase mode of GD/demo/inference_on_a_image.py:117-142: per image, for every phrase (a row of its
+        positive map) the queries whose phrase score sum_t sigmoid(logit[q, t]) * positive_map[p, t] exceeds
+        box_threshold, in phrase order, then query order, as the reference concatenates them.
+        -> [(boxes cxcywh f32 [n, 4] normalised, scores f32 [n], phrase index int64 [n])]."""
+        B = len(images_u8)
+        pm, n_cls, counts = self._positive_maps(positive_maps, B)
+        logits, boxes = self.forward(images_u8)
+        prob = ops.class_scores(logits, pm, n_cls)
+        both = torch.cat([prob, boxes], dim=-1).cpu()         # single D2H copy
+        P, res = prob.shape[-1], []
+        for b in range(B):
+            bx, sc, ph = [], [], []
+            for p in range(counts[b]):
+                keep = both[b, :, p] > box_threshold
+                bx.append(both[b, keep, P:])
+                sc.append(both[b, keep, p])
+                ph.append(torch.full((int(keep.sum()),), p, dtype=torch.int64))
+            res.append((torch.cat(bx), torch.cat(sc), torch.cat(ph)))
+        return res
+
     # ------------------------------------------------------------------ HIP graphs (latency mode)
     # At batch 1 the forward is ~600 small launches whose dependency chain is launch-latency-bound: 11.4 ms eager
     # vs 6.4 ms as a graph replay on MI355X (tools/latency_b1.py); at batch 8 the GPU work dominates and a graph

@@ -1169,6 +1169,40 @@ def topk_rowmax(logits: torch.Tensor, K: int, want_values: bool = False):
     return (idx, val) if want_values else idx
 
 
+def class_scores(logits: torch.Tensor, pos_map: torch.Tensor, n_cls: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """prob[b, q, c] = sum_t sigmoid(logits[b, q, t]) * pos_map[c, t] (csrc/closed_set.hip): logits f32 [B, nq, T] whose
+    rows may be a slice of wider ones (stride(1) >= T, as forward returns them for T % 4 != 0), pos_map f32 [C, T] for
+    every image or [B, C, T] per image, n_cls int32 [B]: classes c >= n_cls[b] score -1.0.  -> f32 [B, nq, C]."""
+    assert logits.dtype == F32 and logits.dim() == 3 and pos_map.dtype == F32 and pos_map.is_contiguous()
+    B, nq, T = logits.shape
+    assert logits.stride(2) == 1 and (B == 1 or logits.stride(0) == nq * logits.stride(1)), "rows (b, q): one strided matrix"
+    assert pos_map.dim() in (2, 3) and pos_map.shape[-1] == T and (pos_map.dim() == 2 or pos_map.shape[0] == B)
+    Cn = pos_map.shape[-2]
+    if n_cls is not None:
+        assert n_cls.dtype == torch.int32 and n_cls.is_contiguous() and tuple(n_cls.shape) == (B,)
+    if out is None:
+        out = torch.empty((B, nq, Cn), device=logits.device, dtype=F32)
+    assert out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (B, nq, Cn)
+    check(_lib.lib().ink_class_scores(_p(logits), logits.stride(1), _p(pos_map), Cn * T if pos_map.dim() == 3 else 0,
+                                      _p(n_cls), B, nq, T, Cn, _p(out), _stream()), "ink_class_scores")
+    return out
+
+
+def select_boxes(idx: torch.Tensor, boxes: torch.Tensor, scale_wh: torch.Tensor, Cmax: int):
+    """The selected (query, class) pairs idx int32 [B, K] (= query * Cmax + class) of boxes f32 [B, nq, 4] cxcywh ->
+    (xyxy boxes f32 [B, K, 4] times scale_wh f32 [B, 2] = (w, h), labels int32 [B, K], queries int32 [B, K])."""
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2
+    assert boxes.dtype == F32 and boxes.is_contiguous() and boxes.dim() == 3 and boxes.shape[2] == 4
+    B, K = idx.shape
+    assert boxes.shape[0] == B and scale_wh.dtype == F32 and scale_wh.is_contiguous() and tuple(scale_wh.shape) == (B, 2)
+    out = torch.empty((B, K, 4), device=idx.device, dtype=F32)
+    labels, query = torch.empty_like(idx), torch.empty_like(idx)
+    check(_lib.lib().ink_select_boxes(_p(idx), _p(boxes), _p(scale_wh), B, K, boxes.shape[1], Cmax, _p(out), _p(labels),
+                                      _p(query), _stream()), "ink_select_boxes")
+    return out, labels, query
+
+
 def sine_embed4(ref: torch.Tensor, dim_t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     assert ref.dtype == F32 and ref.is_contiguous() and ref.shape[-1] == 4 and dim_t.numel() == 128
     N = ref.numel() // 4

@@ -10,12 +10,15 @@ Parity with HuggingFace is UNPINNED OFFLINE: the bert-base-uncased vocabulary is
 and the installed `transformers` does not build a usable BertTokenizer from a bare vocab file, so the tests check
 hand-worked expectations on a toy vocabulary, not HuggingFace's output.  The token ids are DATA (see text_branch.py):
 without a vocabulary every detector API still takes id lists, and phrases come back as id tuples.
+One exception: BertTokenizerFast (the `tokenizers` library) does load the toy vocabulary, and the ids and character
+offsets of the captions in tests/golden/gdino_classes_small.npz are its output (encode_with_offsets is compared with
+them exactly, tests/test_closed_set_cpu.py).
 """
 from __future__ import annotations
 
 import os
 import unicodedata
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 MAX_CHARS_PER_WORD = 100
 
@@ -92,6 +95,60 @@ def basic_tokenize(text: str) -> List[str]:
     return out
 
 
+def basic_tokenize_with_offsets(text: str) -> List[Tuple[str, List[int]]]:
+    """basic_tokenize, with every character of a token carrying the index in `text` of the character it came from:
+    [(token, [index per character])].  Lower-casing and accent stripping are done per original character (a stripped
+    accent leaves its base character's index; a character whose lower-case form is several characters gives them all
+    its index), so the indices always point into `text` as it was given."""
+    words: List[List[int]] = []
+    cur: List[int] = []
+    for i, ch in enumerate(text):
+        cp = ord(ch)
+        if cp == 0 or cp == 0xFFFD or _is_control(ch):
+            continue                                   # removed without ending a word, as basic_tokenize's clean-up
+        if _is_cjk(cp) or _is_whitespace(ch) or ch.isspace():      # (str.split's own idea of a space included)
+            if cur:
+                words.append(cur)
+            cur = []
+            if _is_cjk(cp):
+                words.append([i])
+        else:
+            cur.append(i)
+    if cur:
+        words.append(cur)
+    out: List[Tuple[str, List[int]]] = []
+    for idxs in words:
+        lowered = "".join(text[i] for i in idxs).lower()      # of the WORD: str.lower looks at context (final sigma)
+        chars: List[Tuple[str, int]] = []
+        for i in idxs:
+            chars += [(c, i) for c in text[i].lower()]
+        if len(lowered) == len(chars):
+            chars = [(c, i) for c, (_, i) in zip(lowered, chars)]
+        norm = [(c, i) for ch, i in chars for c in unicodedata.normalize("NFD", ch) if unicodedata.category(c) != "Mn"]
+        tok, where = "", []
+        for c, i in norm:
+            if _is_punctuation(c):
+                if tok:
+                    out.append((tok, where))
+                out.append((c, [i]))
+                tok, where = "", []
+            else:
+                tok += c
+                where.append(i)
+        if tok:
+            out.append((tok, where))
+    return out
+
+
+def char_to_token(offsets: Sequence[Tuple[int, int]], i: int) -> Optional[int]:
+    """BatchEncoding.char_to_token over WordPiece.encode_with_offsets' offsets: the index of the token whose half-open
+    span contains character i; None for whitespace or a position outside the caption ([CLS] / [SEP] span nothing)."""
+    for k, (s, e) in enumerate(offsets):
+        if s <= i < e:
+            return k
+    return None
+
+
 class WordPiece:
     """tokenizer(caption) -> ids and decode(ids) -> str over one vocab.txt (one token per line, the line number its id)."""
 
@@ -136,6 +193,27 @@ class WordPiece:
         return [self.cls] + [self.vocab[p] for p in self.tokenize(text)] + [self.sep]
 
     __call__ = encode
+
+    def encode_with_offsets(self, caption: str, preprocess: bool = True) -> Tuple[List[int], List[Tuple[int, int]]]:
+        """encode's ids, and for each the half-open character span (start, end) it covers in the string that was
+        tokenized - preprocess_caption(caption) with preprocess, the caption itself without - as a fast tokenizer's
+        offset mapping gives them: [CLS] and [SEP] get (0, 0), a "##" piece the characters it continues with, an [UNK]
+        its whole word.  Lower-casing and accent stripping leave the spans on the ORIGINAL characters."""
+        text = preprocess_caption(caption) if preprocess else caption
+        ids, offsets = [self.cls], [(0, 0)]
+        for word, where in basic_tokenize_with_offsets(text):
+            pieces = self.wordpiece(word)
+            if pieces == ["[UNK]"]:
+                ids.append(self.unk)
+                offsets.append((where[0], where[-1] + 1))
+                continue
+            at = 0
+            for p in pieces:
+                n = len(p) - 2 if at else len(p)       # a continuation piece carries "##"
+                ids.append(self.vocab[p])
+                offsets.append((where[at], where[at + n - 1] + 1))
+                at += n
+        return ids + [self.sep], offsets + [(0, 0)]
 
     def decode(self, ids: Sequence[int]) -> str:
         """Tokens joined by spaces, "##" pieces merged, then clean_up_tokenization's replacements."""
