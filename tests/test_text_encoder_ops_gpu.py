@@ -10,21 +10,11 @@ import torch
 
 import text_encoder_ref as R
 from attn_few_ref import TOL_FEWQ
+from row_kernels_ref import check_split as _check_split
 
 pytestmark = pytest.mark.gpu
 
 F16, F32, I32 = torch.float16, torch.float32, torch.int32
-
-
-def _check_split(split, f32, what):
-    """split f16 [rows, 3C] against f32 [rows, C] of the same launch."""
-    C = f32.shape[1]
-    hi, lo, hs = (split[:, i * C:(i + 1) * C] for i in range(3))
-    assert torch.equal(hi, f32.to(F16)), what
-    assert torch.equal(hs, (hi.float() / 64.0).to(F16)), what
-    rec = hi.double() + lo.double() / 64.0
-    err = (rec - f32.double()).abs()
-    assert (err <= 2.0 ** -21 * f32.double().abs() + 2.0 ** -31).all(), (what, err.max().item())
 
 
 # ---------------------------------------------------------------------------------------------------------------
