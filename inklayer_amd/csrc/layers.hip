@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void lay_chamfer_thresh_kernel(const int* __re
   const int y = word / Wp, w = word - y * Wp, x = w * 64 + lane;
   const int mv = minv[blockIdx.y];
   int shrink = 0;
-  if (mv < CH_INF) {
+  if (mv <= CH_INF) {                                        // above CH_INF: no stroke pixel at all (the memset value)
     shrink = (int)floorf((float)mv * (1.0f / 65536.0f)) - margin;
     if (shrink < 0) shrink = 0;
   }

@@ -1370,7 +1370,12 @@ LAYERS_MODES = {"flood": 0, "fill_all": 1, "fill_rule": 2, "largest": 3}
 
 def layers_components(planes: torch.Tensor, W: int, mode: str) -> Tuple[torch.Tensor, torch.Tensor]:
     """One component pass of get_mask (see ink_layers_components) -> (planes, workspace header int32 [514]:
-    [0] overflow flag, [1] number of undecided holes of mode 'fill_rule', then their 8-int records)."""
+    [0] overflow flag, [1] number of undecided holes of mode 'fill_rule', then their 8-int records).
+
+    Mode 'largest' ranks components by a closed-form contour area that holds for components WITHOUT enclosed background;
+    the caller guarantees it (get_mask hands over the complement of the corner flood, which has none).
+    Mode 'fill_rule' records at most 64 undecided holes PER CALL, summed over all planes of the batch: [1] keeps
+    counting beyond that, the records of the surplus are lost, and layers._resolve_undecided refuses such a header."""
     n, H = _check_planes(planes, W)
     need = C.c_int64(0)
     check(_lib.lib().ink_layers_components_workspace_ints(n, H, W, C.byref(need)), "ink_layers_components_workspace_ints")
