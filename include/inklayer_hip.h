@@ -588,8 +588,8 @@ int ink_select_boxes(const int32_t* idx, const float* boxes, const float* scale_
  *   area > area_threshold (500) OR max(w,h) / (min(w,h) + 1e-5) > aspect_threshold (1.1).
  * masks_u8 / out_u8: [n, H, W] uint8 (any value > 127 is foreground on input; 0 / 255 on output), the masks stay in
  * HBM instead of travelling through masks/mask_i.png -> masks_cleaned/mask_i.png (runner.py:57-60,69).
- * tmp_a / tmp_b: [n, H, W] uint8 scratch; workspace: int32[ink_mask_cleanup_workspace_ints(n, H, W, k)].
- * H, W <= 16383. */
+ * tmp_a / tmp_b: [n, H, W] uint8 scratch (tmp_a 8-byte aligned); workspace: int32[ink_mask_cleanup_workspace_ints(n, H,
+ * W, k)].  8 <= W <= 16383, H <= 16383; a refused call launches nothing. */
 int ink_mask_cleanup_workspace_ints(int32_t n, int32_t H, int32_t W, int32_t k, int64_t* out_ints);
 int ink_mask_cleanup(const void* masks_u8, int32_t n, int32_t H, int32_t W, int32_t k, int32_t area_threshold,
                      double aspect_threshold, void* tmp_a_u8, void* tmp_b_u8, int32_t* workspace, void* out_u8,

@@ -152,6 +152,11 @@ extern "C" int ink_mask_cleanup(const void* masks_u8, int32_t n, int32_t H, int3
   uint8_t* b = (uint8_t*)tmp_b_u8;
   const size_t lds = (size_t)(W + 1) * sizeof(int);
   INK_CHECK_ARG(lds <= 64 * 1024);
+  // The components pass packs the closed masks into bit planes that live in the first scratch image: 8 ceil(W/64) <= W
+  // bytes per row from W = 8 on.  Checked here, before the first launch, so that a refused call has done nothing.
+  const int Wp = (W + 63) / 64;
+  INK_CHECK_ARG((int64_t)Wp * 8 <= (int64_t)W);
+  INK_CHECK_ARG(ink_aligned<8>(tmp_a_u8));
   const int seg = 128;
   const dim3 cgrid((W + 255) / 256, (H + seg - 1) / seg, n);
   // dilate: rows (threshold > 127, cv2.threshold) then columns; erode: rows then columns
@@ -160,13 +165,9 @@ extern "C" int ink_mask_cleanup(const void* masks_u8, int32_t n, int32_t H, int3
   hipLaunchKernelGGL(box_rows_kernel, dim3(n * H), dim3(256), lds, s, b, a, W, r, 1, 0);
   hipLaunchKernelGGL(box_cols_kernel, cgrid, dim3(256), 0, s, a, b, H, W, r, 1, seg);
   // 8-connected components of the closed masks with area / aspect filter: the closed 0/1 bytes are packed into bit
-  // planes (they live in the first scratch image, which is free again: 8 ceil(W/64) <= W bytes per row from W = 8 on)
-  // and labelled by the multi-workgroup run-based passes of bitplane.h; the kept runs are painted straight into
-  // out_u8 as 0 / 255.
-  const int Wp = (W + 63) / 64;
-  INK_CHECK_ARG((int64_t)Wp * 8 <= (int64_t)W);
+  // planes (they live in the first scratch image, which is free again) and labelled by the multi-workgroup run-based
+  // passes of bitplane.h; the kept runs are painted straight into out_u8 as 0 / 255.
   u64* planes = (u64*)a;
-  INK_CHECK_ARG(ink_aligned<8>(planes));
   hipLaunchKernelGGL(bp_pack_kernel, dim3((H * Wp + 3) / 4, n), dim3(256), 0, s, (const uint8_t*)b, H, W, Wp, 0, planes);
   if (hipMemsetAsync(workspace, 0, sizeof(int32_t), s) != hipSuccess) return INK_ERR_LAUNCH;
   return cc_run(planes, (int64_t)H * Wp, n, H, W, Wp, cleanup_rm(W, k), 1, area_threshold, aspect_threshold,

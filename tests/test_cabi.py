@@ -136,8 +136,8 @@ def test_refine_stage_argument_contract():
 def _misaligned_cases():
     """name -> (well-formed arguments with fake pointers, {pointer argument: the alignment its entry point demands})
     for the entry points whose pointer checks go through ink_aligned (csrc/common.h) and that no other test module
-    feeds a misaligned pointer.  Not here because the check cannot fail a call before a launch: ink_mask_cleanup
-    (refine.hip: the pointer is derived from the workspace after the first passes), and the alignment tests of
+    feeds a misaligned pointer.  Not here: ink_mask_cleanup (tests/test_mask_handoff_ops_gpu.py feeds it a misaligned
+    scratch image), and, because the check cannot fail a call before a launch, the alignment tests of
     msda.hip, visualize.hip, ink_sam_postprocess and ink_eval_*'s vector paths, which choose a kernel, not an error
     (tests/test_visualize_gpu.py, tests/test_evaluate_gpu.py feed those misaligned buffers)."""
     p = 4096

@@ -12,7 +12,6 @@ ROOT = Path(__file__).resolve().parent.parent
 
 # wrapper -> why it needs no `ops.<name>` call of its own
 EXEMPT = {
-    "mask_cleanup": "called through refine.clean_masks, which tests/test_refine_gpu.py checks bit-exactly against the oracle",
     "_resize_u8": "private: the one C call behind ops.resize_bilinear_u8 and ops.inp_resize_u8, which tests/test_resize.py "
                   "and tests/test_inpaint_gpu.py check against Pillow bit for bit",
 }
