@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import amg_ref as R
+from amg_cases import pack_planes, smooth_noise, unpack_planes
 import sam_prompt_ref as PR
 
 pytestmark = pytest.mark.gpu
@@ -45,15 +46,6 @@ def embs():
 
 
 # ------------------------------------------------------------------------------------------------ data
-def smooth_noise(seed, n, h, w, k=9, scale=14.0, bias=1.5):
-    """Box-filtered noise scaled to a few units minus a bias: each mask a handful of blobs that both stability
-    thresholds cut through."""
-    rs = np.random.RandomState(seed)
-    x = torch.from_numpy(rs.standard_normal((n, 1, h, w)).astype(np.float32))
-    ker = torch.ones(1, 1, k, k) / (k * k)
-    return (torch.nn.functional.conv2d(x, ker, padding=k // 2)[:, 0] * scale - bias).contiguous()
-
-
 def stats_logits(seed, n=6):
     """low-res logits [n + 2, 256, 256]: blobs kept away from the frame border (interior boxes that differ per mask),
     one all-negative and one all-positive mask."""
@@ -87,26 +79,6 @@ def blob_batch(seed, low_hw, crop_hw):
     iou = (0.88 + rs.uniform(-0.05, 0.12, (64, 3))).astype(np.float32)
     points = R.build_point_grid(8) * np.array(crop_hw)[None, ::-1]
     return torch.from_numpy(low), torch.from_numpy(iou), points
-
-
-def unpack_planes(planes, H):
-    """column-major bit planes int64 [m, W, ceil(H / 64)] -> bool [m, H, W]"""
-    p = planes.cpu().numpy().view(np.uint64)
-    bits = (p[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
-    m, W, hp, _ = bits.shape
-    full = bits.reshape(m, W, hp * 64)
-    assert not full[:, :, H:].any(), "bits of rows >= H must be zero"
-    return torch.from_numpy(full[:, :, :H].astype(bool).transpose(0, 2, 1).copy())
-
-
-def pack_planes(masks, dev):
-    """bool [m, H, W] -> column-major bit planes on the device (test-side construction of hand-made planes)"""
-    m, H, W = masks.shape
-    hp = -(-H // 64)
-    pad = np.zeros((m, W, hp * 64), dtype=np.uint64)
-    pad[:, :, :H] = masks.numpy().transpose(0, 2, 1)
-    words = (pad.reshape(m, W, hp, 64) << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
-    return torch.from_numpy(words.view(np.int64)).to(dev)
 
 
 def ref_table(logits, thr, off):
